@@ -7,7 +7,7 @@ Workload C2 (BASELINE.json configs[1]): one 12-MP RPi-HQ frame (3040 x 4056 x 3,
 6144 x 8192) per GPU, ADMM-TV, 100 iterations.  A "step" is one full 100-iteration
 reconstruction (`apply(n_iter=100)`) of one frame per GPU with inputs resident in HBM.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Multi-GPU: frames are independent, so rank r reconstructs its own frame (weak scaling, no
@@ -15,7 +15,16 @@ collective inside the loop); one RCCL all-gather of the final images closes each
 path would do when a batch is sharded over the node.  value = total iterations of all ranks /
 max-over-ranks wall time.
 
-Rank 0 prints ONE JSON line.  On top of the driver's contract it carries:
+A plain run sets up, warms up, times --steps steps (no HIP events inside them), writes the last step's
+outputs if --dump-outputs is given, and prints the result line: metric, value, unit, ms_per_step (wall
+milliseconds of one timed step), higher_is_better, dtype, the workload and the launch plan.
+
+--dump-outputs DIR: what the timed path handed its caller in its last step, as DIR/<name>.npy (float32;
+float64 for --dtype float64); an array beyond its share of 48 MB is written as a fixed sample, the
+elements at seeded random flat indices (the same ones in every run with the same arguments).  The
+inputs are closed-form or seeded, so two builds can be compared output for output.
+
+--full adds everything else the benchmark measures and checks; rank 0's line then also carries:
   roofline      ADMM prox / dual-update kernel (the TV / W half of the image-domain work, 8R per launch: reads V,
                 eta0, eta1, rho, writes eta0, eta1, rho, r_sp -- the duals travel half-applied between the iterations
                 of a call, so V_old is read by the first launch of a call only (9R: 1 launch in 100; the figure is
@@ -32,6 +41,11 @@ Rank 0 prints ONE JSON line.  On top of the driver's contract it carries:
                 reference in float64 and float32): distance to the reference's float64 run, the reference's own float32
                 distance to it, PSNR delta vs the scene.  No CPU solver runs for it (tests/test_longrun_pins.py asserts the
                 same, and more, in the GPU suite).
+  other_configs short legs of the BASELINE configs the headline does not cover (C1, C3, C4, C5, float64, off-list shapes)
+  all_gather_ms with several ranks: the collective timed on its own (after the check that a rank's slot of the last
+                gather is its own result)
+--no-cpu-baseline, --no-parity and --no-other-configs leave single legs of --full out.  Since --full brackets the
+roofline kernel's launches inside the timed region, its `value` carries their cost; a plain run's does not.
 """
 import argparse
 import json
@@ -144,20 +158,46 @@ def parse():
                     help="skip the short C1 / C3 / C4 / C5 legs reported under 'other_configs'")
     ap.add_argument("--test-shape", type=lambda v: tuple(int(x) for x in v.split(",")), default=None,
                     help="tests only (LPC_BENCH_BACKEND=emu): B,D,H,W,n_iter replacing the sizes of --config c4 / c5-planes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (a fixed, seeded sample beyond 48 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline / per-kernel figures, the device-copy yardstick, the all-gather on its own, the "
+                         "parity against the reference's samples, the CPU baseline and the other BASELINE configs")
     return ap.parse_args()
 
 
-def synth_inputs(H, W, C, seed, device):
+def synth_inputs(H, W, C, seed, device, with_scene=True):
     """Closed-form inputs (tests/golden/longrun_inputs.py; exact float32 operations, the same bits on every machine):
     PSF = uniform**12 scaled to unit energy (lensless/utils/io.py:375), measurement = broad bumps + sensor
-    noise, clipped and divided by its maximum (io.py:196-197), scene = what PSNR is quoted against.  Rank r (seed r)
-    gets its own measurement; seed 0 is the frame the reference's 100-iteration run is on file for."""
+    noise, clipped and divided by its maximum (io.py:196-197), scene = what PSNR is quoted against (None unless
+    `with_scene`: only the parity leg needs it).  Rank r (seed r) gets its own measurement; seed 0 is the frame the
+    reference's 100-iteration run is on file for."""
     sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
     import longrun_inputs as li
 
     psf = torch.from_numpy(li.psf12(1, H, W, C, seed=0)).to(device)
     y = torch.from_numpy(li.measurement(H, W, C, seed=seed)).to(device)
-    return psf, li.scene(H, W, C), y
+    return psf, li.scene(H, W, C) if with_scene else None, y
+
+
+DUMP_BUDGET = 48 << 20      # bytes over all files of --dump-outputs: the 148-MB C2 frame is written as a sample
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array the timed path handed its caller, float32 (float64 stays float64).  An
+    array beyond its share of DUMP_BUDGET is written as a fixed sample: the elements at seeded random flat indices (numpy
+    seed 0, sorted, duplicates dropped), the same elements in every run with the same arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        k = share // (8 if dt == torch.float64 else 4)
+        if t.numel() > k:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), k))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, f"{name}.npy"), t.to(dt).cpu().numpy())
+    log(f"outputs written to {dirname}: {', '.join(sorted(arrays))}")
 
 
 def reference_parity(out, scene, H, W, n_iter, algo):
@@ -239,10 +279,15 @@ def run_c4(args, rank, world, dev, dist):
     lo, hi = shard_bounds(B, world, rank)
     elapsed, stats = rank_stats(dist, dev, elapsed, (hi - lo) * n_iter * args.steps)
     assert out.shape == (B, 1, H, W, C)
-    roof, kern = dominant_roofline(sharded.rec._handle, lambda: sharded(frames, n_iter=n_iter), rank == 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"reconstruction": out})
+    extra = {}
+    if args.full:
+        roof, kern = dominant_roofline(sharded.rec._handle, lambda: sharded(frames, n_iter=n_iter), rank == 0)
+        extra = {"roofline": roof, "kernels": kern}
     if rank == 0:
         emit({
-            "roofline": roof, "kernels": kern,
+            **extra,
             "metric": "ADMM frame-iterations/sec, batch of 64 frames 270x480x3, 20 iters (BASELINE config 4)",
             "value": round(B * n_iter * args.steps / elapsed, 1), "unit": "frame-iterations/s", "n_gpus": world,
             "steps": args.steps, "warmup": max(args.warmup, 1), "ms_per_step": round(elapsed / args.steps * 1e3, 3),
@@ -277,15 +322,20 @@ def run_c5_planes(args, rank, world, dev, dist):
     lo, hi = shard_bounds(D * C, world, rank)
     elapsed, stats = rank_stats(dist, dev, elapsed, (hi - lo) * n_iter * args.steps)
     assert out.shape == (D, H, W, C)
-    first = next(iter(sharded._solvers.values()), None)          # (a rank without units has no solver: rank 0 always has)
-    if first is not None:
-        roof, kern = dominant_roofline(first._handle, lambda: sharded(y, n_iter=n_iter), rank == 0)
-    else:
-        sharded(y, n_iter=n_iter)
-        roof = kern = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"reconstruction": out})
+    extra = {}
+    if args.full:
+        first = next(iter(sharded._solvers.values()), None)      # (a rank without units has no solver: rank 0 always has)
+        if first is not None:
+            roof, kern = dominant_roofline(first._handle, lambda: sharded(y, n_iter=n_iter), rank == 0)
+        else:
+            sharded(y, n_iter=n_iter)
+            roof = kern = None
+        extra = {"roofline": roof, "kernels": kern}
     if rank == 0:
         emit({
-            "roofline": roof, "kernels": kern,
+            **extra,
             "metric": "ADMM iterations/sec, one 1080x1920x3 frame against 16 depth planes, 50 iters (BASELINE config 5), "
                       "its 48 planes sharded over the GPUs",
             "value": round(n_iter * args.steps / elapsed, 2), "unit": "iterations/s", "n_gpus": world,
@@ -523,7 +573,7 @@ def main():
 
     H, W, C, n_iter = args.height, args.width, 3, args.n_iter
     log("generating synthetic inputs")
-    psf, scene, y = synth_inputs(H, W, C, rank, dev)
+    psf, scene, y = synth_inputs(H, W, C, rank, dev, with_scene=args.full)
     if args.dtype == "float64":
         psf, y = psf.double(), y.double()
     RT.sync()
@@ -562,10 +612,11 @@ def main():
     wait_gather()
     RT.sync()
     log("timed region")
-    # HIP events inside the timed region only around the kernel the roofline reports: bracketing all six to eight launches
-    # of an iteration costs the timed rate 1.4 % (ADMM) to 3.4 % (FISTA) (tools/probe/event_overhead.py); the other kernels'
-    # rows of `kernels` come from one more step after the clock has stopped
-    rec._handle.profile_enable(True, kernels=["spatial", "row_fwd"] if args.algo == "admm" else ["spatial"])
+    if args.full:
+        # HIP events inside the timed region only around the kernel the roofline reports: bracketing all six to eight
+        # launches of an iteration costs the timed rate 1.4 % (ADMM) to 3.4 % (FISTA) (tools/probe/event_overhead.py); the
+        # other kernels' rows of `kernels` come from one more step after the clock has stopped.  A plain run brackets none.
+        rec._handle.profile_enable(True, kernels=["spatial", "row_fwd"] if args.algo == "admm" else ["spatial"])
     if dist:
         dist.barrier()
     RT.sync()
@@ -578,6 +629,48 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     elapsed, rstats = rank_stats(dist, dev, elapsed, args.steps * n_iter)
+    log(f"timed region done: {elapsed:.3f} s for {args.steps} step(s)")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"reconstruction": gathered if dist else out})
+
+    result = None
+    if rank == 0:
+        total_iters = world * args.steps * n_iter
+        result = {
+            "metric": "ADMM iterations/sec at 4056x3040x3, 100 iters" if args.algo == "admm"
+            else "FISTA iterations/sec at 4056x3040x3",
+            "value": round(total_iters / elapsed, 3),
+            "unit": "iterations/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32" if args.dtype == "float32" else "f64",
+            "data": "synthetic",
+            "config": {
+                "workload": f"C2: one {H}x{W}x{C} frame per GPU, {args.algo.upper()}"
+                            f"{'-TV' if args.algo == 'admm' else ''} {n_iter} iterations per step",
+                "frame": [H, W, C], "padded_fft_frame": [hp, wp], "n_iter": n_iter,
+                "frames_per_gpu": 1, "parallelism": f"frames sharded over {world} GPU(s), one all-gather per step",
+            },
+            "backend": RT.name,
+            "hbm_workspace_GB": round(rec._handle.workspace_bytes() / 1e9, 2),
+            "engine_plan": rec._handle.plan_info(),
+            "all_gather_MB_per_rank": round(H * W * C * (8 if args.dtype == "float64" else 4) / 1e6, 2),
+            **rstats,
+        }
+    if not args.full:
+        if rank == 0:
+            emit(result)
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything below measures or checks more than the headline figure needs ------------------------------
     gather_ms = None
     if dist:
         assert torch.equal(gathered[rank:rank + 1], out)      # this rank's slot of the last gather is its own result
@@ -586,7 +679,6 @@ def main():
         dist.all_gather_into_tensor(gathered, send)
         gather_ms = RT.timed_ms(lambda: dist.all_gather_into_tensor(gathered, send), 3)
     prof_live = rec._handle.profile_read()
-    log(f"timed region done: {elapsed:.3f} s for {args.steps} step(s)")
     rec._handle.profile_enable(True)
     step()
     wait_gather()
@@ -606,10 +698,8 @@ def main():
         copy_gbps = 2 * src_buf.numel() * 4 / (RT.timed_ms(lambda: dst_buf.copy_(src_buf), 10) * 1e-3) / 1e9
         del src_buf, dst_buf
 
-    result = None
     if rank == 0:
         total_iters = world * args.steps * n_iter
-        value = total_iters / elapsed
         kid = _native.K_SPATIAL
         kbytes = rec._handle.kernel_bytes(kid)
         k_ms, k_n = prof["spatial"]
@@ -634,26 +724,7 @@ def main():
                         "bytes": round(cb * 1e9), "ms": round(cm, 4), "achieved": round(cb / (cm * 1e-3), 1),
                         "frac": round(cb / (cm * 1e-3) / HBM_PEAK_GBS, 4)}
         moved_gb = sum(v["alg_GB"] for v in kernels.values())
-        result = {
-            "metric": "ADMM iterations/sec at 4056x3040x3, 100 iters" if args.algo == "admm"
-            else "FISTA iterations/sec at 4056x3040x3",
-            "value": round(value, 3),
-            "unit": "iterations/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32" if args.dtype == "float32" else "f64",
-            "data": "synthetic",
-            "config": {
-                "workload": f"C2: one {H}x{W}x{C} frame per GPU, {args.algo.upper()}"
-                            f"{'-TV' if args.algo == 'admm' else ''} {n_iter} iterations per step",
-                "frame": [H, W, C], "padded_fft_frame": [hp, wp], "n_iter": n_iter,
-                "frames_per_gpu": 1, "parallelism": f"frames sharded over {world} GPU(s), one all-gather per step",
-            },
+        result.update({
             "roofline": {
                 "bound": "hbm",
                 "kernel": ("LPC_K_SPATIAL = ADMM prox / dual-update kernel; split of the image-domain work: "
@@ -678,14 +749,9 @@ def main():
                 "on_survey_model_bytes": round(rec._handle.model_bytes() * total_iters / world / elapsed / 1e9 / HBM_PEAK_GBS, 4),
                 "on_bytes_moved": round(moved_gb * total_iters / world / elapsed / HBM_PEAK_GBS, 4),
                 "survey_model_GB": round(rec._handle.model_bytes() / 1e9, 3), "bytes_moved_GB": round(moved_gb, 3)},
-            "backend": RT.name,
             "device_copy_GBps": round(copy_gbps, 1) if copy_gbps else None,
-            "hbm_workspace_GB": round(rec._handle.workspace_bytes() / 1e9, 2),
-            "engine_plan": rec._handle.plan_info(),
             "all_gather_ms": round(gather_ms, 3) if gather_ms is not None else None,
-            "all_gather_MB_per_rank": round(H * W * C * (8 if args.dtype == "float64" else 4) / 1e6, 2),
-            **rstats,
-        }
+        })
 
     if rank == 0 and not args.no_parity and args.dtype == "float32":
         par = reference_parity(out, scene, H, W, n_iter, args.algo)

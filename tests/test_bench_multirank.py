@@ -11,19 +11,21 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(emu_lib, extra, nproc=2):
+def _run(emu_lib, extra, nproc=2, full=True):
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
     env = dict(os.environ, LPC_BENCH_BACKEND="emu", LPC_EMU_THREADS="2", PYTHONPATH=ROOT)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "2", "--warmup", "1"] + extra
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "2", "--warmup", "1"] + \
+        (["--full"] if full else []) + extra
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -59,3 +61,31 @@ def test_sharded_configs_two_ranks(emu_lib, config, shape, unit):
     j = _run(emu_lib, ["--config", config, "--test-shape", shape])
     _common(j, 2)
     assert j["scaling"] == "strong" and j["unit"] == unit
+
+
+def test_plain_line_and_dumped_outputs(emu_lib, tmp_path, monkeypatch):
+    """Without --full the line carries the headline figure and nothing that needs more runs (no roofline, no per-kernel rows,
+    no collective timed on its own); --dump-outputs writes what the timed path handed its caller in its last step: the
+    gathered frames, each equal to the single-frame solver on that rank's closed-form inputs."""
+    import torch
+
+    import lenslesspicam_amd as lpa
+    from lenslesspicam_amd import recon
+
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import longrun_inputs as li
+
+    j = _run(emu_lib, ["--height", "20", "--width", "24", "--n-iter", "3", "--dump-outputs", str(tmp_path / "out")], full=False)
+    _common(j, 2)
+    assert j["scaling"] == "weak" and j["unit"] == "iterations/s" and j["dtype"] == "f32"
+    assert abs(j["value"] - 2 * 2 * 3 / (j["ms_per_step"] * 2 / 1e3)) <= 1e-3 * j["value"]
+    assert not {"roofline", "kernels", "all_gather_ms", "device_copy_GBps", "cpu_baseline", "parity", "other_configs"} & set(j)
+    assert os.listdir(tmp_path / "out") == ["reconstruction.npy"]
+    got = np.load(tmp_path / "out" / "reconstruction.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 20, 24, 3)
+    monkeypatch.setattr(recon, "runtime", lambda dtype="float32": (emu_lib, torch.device("cpu")))
+    for r in range(2):
+        rec = lpa.ADMM(torch.from_numpy(li.psf12(1, 20, 24, 3, seed=0)), n_iter=3)
+        rec.set_data(torch.from_numpy(li.measurement(20, 24, 3, seed=r)))
+        want = rec.apply(n_iter=3, disp_iter=None, plot=False).numpy()[0]
+        np.testing.assert_allclose(got[r], want, rtol=0, atol=1e-6 * np.abs(want).max())

@@ -231,7 +231,7 @@ def _torchrun_bench(extra, port):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"] + extra
+           "--gpus", "1", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"] + extra
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

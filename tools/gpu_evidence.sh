@@ -11,11 +11,11 @@ for cfg in "c2:" "c4:--config c4" "c3:--algo fista"; do
   cp profiles/${tag}_${t}_counters.md profiles/${tag}_${t}_kernel_stats.csv $out/ 2>/dev/null
 done
 cp profiles/traffic.json $out/
-(time python bench.py > $out/bench.json 2> $out/bench.log); tail -2 $out/bench.log
+(time python bench.py --full > $out/bench.json 2> $out/bench.log); tail -2 $out/bench.log
 python tools/kernel_summary.py $out/bench.json; python tools/other_summary.py $out/bench.json
-python bench.py --algo fista --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs > $out/bench_fista.json 2> $out/bench_fista.log
+python bench.py --full --algo fista --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs > $out/bench_fista.json 2> $out/bench_fista.log
 python tools/kernel_summary.py $out/bench_fista.json
-python bench.py --dtype float64 --steps 2 --no-cpu-baseline --no-other-configs > $out/bench_f64.json 2> $out/bench_f64.log
+python bench.py --full --dtype float64 --steps 2 --no-cpu-baseline --no-other-configs > $out/bench_f64.json 2> $out/bench_f64.log
 python tools/kernel_summary.py $out/bench_f64.json
 python tools/profile_admm.py > $out/profile.log 2>&1; python tools/profile_admm.py --algo fista >> $out/profile.log 2>&1; python tools/profile_admm.py --raw >> $out/profile.log 2>&1; cat $out/profile.log
 ls $out | tr '\n' ' '

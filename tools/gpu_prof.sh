@@ -5,7 +5,7 @@
 tag=$1; shift
 out=$PWD/gpurun_out/$tag; mkdir -p $out
 export TMPDIR=/tmp
-B="python $PWD/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-other-configs --n-iter 40 $@"
+B="python $PWD/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-other-configs --n-iter 40 $@"
 cd /tmp
 rocprofv3 --kernel-trace --stats -f csv -d $out/prof_stats -o stats -- $B > $out/prof_bench.json 2> $out/prof_stats.log
 rocprofv3 -f csv --pmc FETCH_SIZE -d $out/prof_fetch -o c -- $B > $out/prof_fetch.log 2>&1
