@@ -218,7 +218,7 @@ static void choose_split(const EngineOpts& opt, int Hp, int Wc, int* N1, int* N2
 }
 
 // stored row p = k1*N2 + k2  <->  frequency k = k1 + N1*k2
-static inline int stored_row_freq(const Engine* e, int p) { return (p / e->N2) + e->N1 * (p % e->N2); }
+static inline int stored_row_freq(const Engine* e, int p) { return (p / e->plan.N2) + e->plan.N1 * (p % e->plan.N2); }
 
 // ---- the launch plan: everything that is decided once per handle, no device work -----------------------------------
 static void set_static_fft(StaticFft& f, int n, const std::vector<int>& rad, int T, int nt, int em) {
@@ -260,23 +260,24 @@ static int plan_cu_count() {
   return rt::cu_count();
 }
 
-// `allow_static`: choose compile-time plans (-> e->spec, served by a plan module) wherever the kernels exist; false: the
-// run-time plans of the core library alone.  Sets N1, N2, T, rows_half and the spec; touches nothing on the device.
-static void choose_plan(Engine* e, bool allow_static) {
+// `allow_static`: choose compile-time plans (-> e->plan.spec, served by a plan module) wherever the kernels exist; false: the
+// run-time plans of the core library alone.  Starts the record afresh and sets N1, N2, T, rows_half and the spec; `cu`:
+// compute units the plan is sized for (plan_cu_count).  Touches nothing on the device.
+static void choose_plan(Engine* e, bool allow_static, int cu) {
   const lpc_config& c = e->cfg;
   const PlaneGeom& g = e->g;
   const EngineOpts& o = e->opt;
   const bool admm = c.algo == LPC_ALGO_ADMM, f32 = sizeof(real) == 4;
-  e->spec = PlanSpec{};
-  e->spec.family = admm ? LPC_FAM_ADMM : LPC_FAM_GD;
-  e->spec.f64 = f32 ? 0 : 1;
-  e->mid_reg = true;
+  LaunchPlan& pl = e->plan;
+  pl = LaunchPlan{};
+  pl.spec.family = admm ? LPC_FAM_ADMM : LPC_FAM_GD;
+  pl.spec.f64 = f32 ? 0 : 1;
   // (a 24-point register middle for ADMM in float32 only: 2 x 24 complex128 values do not fit a lane's registers)
   // (the gradient-descent family keeps 128 x 48 at 6144 rows: its 48-point middle lives in registers)
-  choose_split(o, g.Hp, g.Wc, &e->N1, &e->N2, &e->T, !admm || f32, admm && f32);
+  choose_split(o, g.Hp, g.Wc, &pl.N1, &pl.N2, &pl.T, !admm || f32, admm && f32);
   // the column kernels of a plan module address their tiles with 24-bit row-index x row-step products (k_cols): the step
   // between two rows of one column transform must stay below 2^24 bytes (12 MP: 48 rows x 32.8 KB = 1.6 MB)
-  const long col_step = (long)(e->N1 > 1 ? e->N2 : 1) * g.cpitch * (long)sizeof(real2);
+  const long col_step = (long)(pl.N1 > 1 ? pl.N2 : 1) * g.cpitch * (long)sizeof(real2);
   const bool st_cols = allow_static && col_step < (1L << 24) && g.Hp < (1 << 24) &&
                        (unsigned long long)g.Hp * g.cpitch * sizeof(real2) < (1ULL << 32);   // ... and offsets are 32-bit
   // Single-pass ADMM columns whose two-spectra tile allows only 8 image columns (DiffuserCam-sized frames, 540 padded
@@ -286,7 +287,7 @@ static void choose_plan(Engine* e, bool allow_static) {
   // workgroups for 256 CUs): four 39-KB workgroups of 512 lanes x 9 points per CU inside 64 VGPRs.  (Whole 6144-point
   // columns two at a time through the same kernel -- one launch instead of three per column step -- were built and measured
   // in round 4: 2.25 ms against 1.455 ms; 16-column tiles: 30 % slower.  profiles/HISTORY.md)
-  const bool seq = admm && f32 && st_cols && e->N1 == 1 && e->T == 8 && g.Wc > 8 && (long)g.Hp * 16 <= kMaxTilePoints &&
+  const bool seq = admm && f32 && st_cols && pl.N1 == 1 && pl.T == 8 && g.Wc > 8 && (long)g.Hp * 16 <= kMaxTilePoints &&
                    o.col_t == 0 && o.mid_seq != 0 && ((long)e->P * ((g.Wc + 15) / 16) >= 512 || o.mid_seq == 1);
   // Row passes: one real row per half-length complex transform (k_r*_half kernels) once the
   // paired tile is so large that fewer than 5 workgroups fit a CU's 160 KiB of LDS.  Measured (r01b_notes.md):
@@ -308,18 +309,18 @@ static void choose_plan(Engine* e, bool allow_static) {
   const bool admm_wide = (allow_static && g.Wp % 4 == 0 && o.k1_rows != 0) ? g.Wp > 4096
                                                                             : 5 * LPC_ROW_SMEM_BYTES(g.Wp, 1) > 160 * 1024;
   const bool wide = admm ? admm_wide : (g.Wp >= 2048 || (allow_static && g.Wp >= 128));
-  e->rows_half = half_ok && wide;
-  if (o.rows_half == 0) e->rows_half = false;
-  if (o.rows_half == 1 && half_ok) e->rows_half = true;
+  pl.rows_half = half_ok && wide;
+  if (o.rows_half == 0) pl.rows_half = false;
+  if (o.rows_half == 1 && half_ok) pl.rows_half = true;
   if (!allow_static) return;
 
-  PlanSpec& sp = e->spec;
+  PlanSpec& sp = pl.spec;
   std::vector<int> rad;
   // the X half of the image-domain work moves into the forward rows when the stencil half can run as the tiled
   // four-pixel-lane kernel (k_admm_spatial_v4<.., XHALF = false>): padded width a multiple of 4
   const bool xhalf = admm && g.Wp % 4 == 0;
   // ---- rows
-  if (e->rows_half) {
+  if (pl.rows_half) {
     const int n = g.Wp / 2;
     plan_radices(n, rad);
     if (n == 4096) rad = {16, 16, 16};   // one butterfly per thread and stage, one LDS round trip fewer than 8.8.8.8
@@ -376,24 +377,24 @@ static void choose_plan(Engine* e, bool allow_static) {
   // ---- pass A of a split column transform: 32 columns per tile (256-byte row segments at its long row stride) while
   // the fused middle keeps 16 -- the two passes tile the columns independently.  Same-box A/B at 12 MP with T = 32 for
   // both (profiles/r02_notes.md): pass A 0.578 / 0.575 -> 0.530 / 0.510 ms, the middle 0.655 -> 0.71 ms.
-  if (st_cols && e->N1 > 1) {
-    int T = e->T;
-    if (e->T == 16 && g.Wc >= 256 && o.col_t == 0) T = 32;
+  if (st_cols && pl.N1 > 1) {
+    int T = pl.T;
+    if (pl.T == 16 && g.Wc >= 256 && o.col_t == 0) T = 32;
     if (o.passa_t > 0) T = o.passa_t;
-    while (T > 1 && (long)e->N1 * T > kMaxTilePoints) T /= 2;
-    plan_radices(e->N1, rad);
-    if (e->N1 == 90) rad = {10, 9};      // two stages instead of 6.5.3: 16 x 1080p planes 48.1 -> 46.9 ms per 20 iterations
+    while (T > 1 && (long)pl.N1 * T > kMaxTilePoints) T /= 2;
+    plan_radices(pl.N1, rad);
+    if (pl.N1 == 90) rad = {10, 9};      // two stages instead of 6.5.3: 16 x 1080p planes 48.1 -> 46.9 ms per 20 iterations
                                           // (r03k_ab.log; 9.10, 18.5, 30.3 are slower, and 128 = 16.8 is slower than 8.8.2 at 12 MP)
-    const int pts = e->N1 * T;
+    const int pts = pl.N1 * T;
     int nt = T >= 32 ? 512 : 256;
     while (nt < 1024 && (pts + nt - 1) / nt > 16) nt *= 2;
-    set_static_fft(sp.passA, e->N1, rad, T, nt, (pts + nt - 1) / nt);
+    set_static_fft(sp.passA, pl.N1, rad, T, nt, (pts + nt - 1) / nt);
     if (sp.passA.em > 16) sp.passA = StaticFft{};
   }
   // ---- ADMM's fused middle in LDS (a 24-point pass B lives in registers: k_cols_mid_admm_reg, core library)
-  const bool reg_mid = e->N1 > 1 && e->mid_reg && f32 && e->N2 == 24;
+  const bool reg_mid = pl.N1 > 1 && f32 && pl.N2 == 24;
   if (admm && st_cols && !reg_mid) {
-    const int n = e->N2, T = e->T;
+    const int n = pl.N2, T = pl.T;
     plan_radices(n, rad);
     // 540 = 30.18 side by side (two fat register butterflies, one LDS trip; 184 registers, one workgroup per CU);
     // one spectrum at a time: 6.10.9 inside a 128-register budget = TWO workgroups per CU overlapping one another's
@@ -407,7 +408,7 @@ static void choose_plan(Engine* e, bool allow_static) {
     // 5-iteration call 0.243 -> 0.234 ms (profiles/r04t_ab_c1.log; 30.18 on 1024 lanes 19.8 us, 768 lanes 19.6 us).
     // Only while every workgroup has a CU of its own (256 on an MI355X): two frames = 366 tiles are 6 % SLOWER that way
     // (0.370 -> 0.392 ms, r04t_ab_c1c.log).
-    const bool one_wave_of_tiles = !seq && e->N1 == 1 && (long)e->P * ((g.Wc + T - 1) / T) <= plan_cu_count() && n * 2 * T > 8192;
+    const bool one_wave_of_tiles = !seq && pl.N1 == 1 && (long)e->P * ((g.Wc + T - 1) / T) <= cu && n * 2 * T > 8192;
     if (one_wave_of_tiles && n == 540) rad = {6, 10, 9};
     const int pts = n * (seq ? T : 2 * T);
     int nt = pts <= 4096 ? 256 : (pts <= 9216 ? 512 : 1024);
@@ -436,15 +437,81 @@ static void choose_plan(Engine* e, bool allow_static) {
   }
   // pair-line work spectra (lpc_kernels.h: spec_col): paired rows + a single-pass middle of 8-column tiles, float32 (a tile row
   // of 8 complex128 columns is a whole line already)
-  sp.slay = (admm && f32 && sp.row_kind == LPC_ROWS_PAIRED && sp.mid_kind != LPC_MID_RUNTIME && e->N1 == 1 && sp.mid.T == 8 &&
+  sp.slay = (admm && f32 && sp.row_kind == LPC_ROWS_PAIRED && sp.mid_kind != LPC_MID_RUNTIME && pl.N1 == 1 && sp.mid.T == 8 &&
              o.spec_lay != 0) ? 1 : 0;
   // ... the sequential middle's point-wise constants precombined (k_mid_consts); even padded sizes: the ifftshift phases are
   // +-1, one complex constant per element instead of two (mid_pc = 2)
   sp.mid_pc = (sp.slay && sp.mid_kind == LPC_MID_SEQ && o.mid_pc != 0) ? ((g.Hp % 2 == 0 && g.Wp % 2 == 0) ? 2 : 1) : 0;
 }
 
+// the rest of the launch plan, once the module is loaded or refused (e->mod, g.slay) and the row plan's stage twiddles exist
+static void finish_plan(Engine* e, int cu) {
+  const PlaneGeom& g = e->g;
+  const EngineOpts& o = e->opt;
+  LaunchPlan& pl = e->plan;
+  const bool admm = e->cfg.algo == LPC_ALGO_ADMM, gd = e->cfg.algo >= LPC_ALGO_GD, split = pl.N1 > 1;
+  // The half of the image-domain work that needs no neighbours rides in the module's forward row kernel: the blocks of
+  // `a` compute xi' and a = mu1 X - xi' from xi, HV, HV_old, y themselves (-2R per iteration), the tiled kernel keeps
+  // the stencil half at its own occupancy (without a module: the full stand-alone kernel) ...
+  pl.xhalf_rows = admm && e->mod && e->mod->admm_rows_fwd_x;
+  // ... narrow frames (paired rows of one quad per lane: padded widths up to 1024) hand it the TV / W half too: three
+  // launches per iteration, r_sp never stored.  One small frame is a chain of launch boundaries and memory latencies
+  // (C1 -7.6 %), a batch saves the trip of r_sp through memory and the tiled kernel's launch (C4 -6.3 %);
+  // profiles/r05_notes.md section 5 (option k1_rows=0: off)
+  // (round 6: rows of TWO quads per lane as well -- padded widths up to 2048: the reference's own profile frame 760 x 1014
+  // gray 0.458 -> 0.442 ms per 5 iterations, 8 frames of 600 x 800 x 3 22.1 -> 20.8 ms per 20; profiles/r06_notes.md.  FOUR
+  // quads per lane -- 12-MP half-length rows -- are slower than the tiled kernel: not built)
+  const bool k1_rows = pl.xhalf_rows && g.Wp % 4 == 0 && e->mod->k1_rows != 0 && o.k1_rows != 0;
+  pl.k1 = k1_rows ? ADMM_K1_ROWS : pl.xhalf_rows ? ADMM_K1_TV_W : g.Wp % 4 == 0 ? ADMM_K1_TILED : ADMM_K1_SCALAR;
+  // duals half-applied between the iterations of one call (option k1_half=0: never)
+  pl.k1_half = pl.xhalf_rows && o.k1_half != 0;
+  // K1Rows::xcd_order.  (The XCD-aware block orders assume the MI355X's 8 XCDs x 32 CUs and its dispatch rule "workgroup w
+  // on XCD w % 8"; any other part gets launch order: the orders are permutations, results are the same.)
+  pl.k1_xcd_order = cu != 256 ? 0 : (long)paired_rows_grid(g, false) * e->P <= 8192 ? -1 : std::max(0, o.k1_group);
+  // ... outside the sensor window that half works from HV alone (AdmmScalars::xiw; option xi_full: every pixel alike) ...
+  pl.xi_window = pl.xhalf_rows && !o.xi_full;
+  // ... and rows wholly outside it skip the H V row transforms in both directions: the kept rows of SB are rescaled by
+  // forward pass A (any plan) or, for single-pass columns, by the module's fused middle (option hv_full: off)
+  pl.hv_skip = pl.xi_window && !o.hv_full && e->mod->admm_rows_inv && (split || e->mod->admm_mid);
+  // ADMM middle.  Two arrays per lane: only short pass-B transforms fit the register file.  Measured at 12 MP
+  // (profiles/r01b_notes.md): 24 points 0.89 ms and 32 points 0.83 ms beat the LDS middle (0.99 / 0.92 ms) but
+  // need a 256- / 192-point pass A that costs more than it saves; 48 points is 1.62 ms (AGPR traffic).
+  // Just above 8192 points (C1 / C4: 540 rows x 8 columns x 2 arrays = 8640): 512 threads x 18 points keeps
+  // TWO workgroups per CU inside the 128-VGPR budget; 1024 x 16 is one 16-wave workgroup per CU in lock-step
+  // at every barrier (C4: middle 1.435 -> 1.331 ms, 17.5k -> 18.0k frame-it/s)
+  const long mid_pts = (long)pl.N2 * pl.T * 2;
+  pl.admm_mid = split && sizeof(real) == 4 && pl.N2 == 24 ? ADMM_MID_REG24
+                : e->mod && e->mod->admm_mid ? ADMM_MID_MODULE
+                : mid_pts > 8192 && mid_pts <= 9216 ? ADMM_MID_RT_512X18 : ADMM_MID_RT_LDS;
+  // convolution middle: one lane = one whole pass-B column transform in registers, for the lengths choose_split produces most
+  static const int kRegMid[] = {48, 40, 36, 32, 30, 24};
+  pl.conv_mid_reg = split && std::find(std::begin(kRegMid), std::end(kRegMid), pl.N2) != std::end(kRegMid) ? pl.N2 : 0;
+  pl.gd_fuse_fwd = gd && e->mod && e->mod->gd_rows_update_fwd && !o.gd_no_fuse_fwd;
+  // the second form of the fused row kernels: 8-byte accesses to y / x need an even window offset and frame width
+  pl.gd_v2 = gd && e->mod && e->mod->gd_v2 && e->tws_row && o.gd_v2 != 0 && ((g.sw | g.W) & 1) == 0 && g.W >= 2;
+  pl.rev_k1 = o.rev_order & 1;
+  pl.rev_passa_fwd = o.rev_order & 2;
+  pl.rev_passa_inv = o.rev_order & 4;
+  pl.rev_mid = o.rev_order & 8;
+  // EngineOpts::gd_rev -1: all three (the row kernels and the register middle alternate with the forward-walking pass A, so
+  // every kernel starts where its predecessor finished): 12 MP FISTA 75.4 / 74.1 / 73.8 -> 74.5 / 73.0 / 72.8 ms per 40 iterations
+  // on three instances of one box against the middle alone (r03z_ab.log); no effect at 1080p, where nothing is reversed
+  const int gd_rev = o.gd_rev >= 0 ? o.gd_rev : ((size_t)g.cplane * e->P * sizeof(real2) > ((size_t)200 << 20)) ? 7 : 0;
+  pl.gd_rev_resid = gd_rev & 1;
+  pl.gd_rev_update = gd_rev & 2;
+  pl.gd_rev_mid = gd_rev & 4;
+  // pairs of column tiles on one XCD: measured (profiles/r03_notes.md) -6 % on the 5-iteration C1 call, whose 8-column
+  // tiles read half cache lines (middle 0.0278 -> 0.0228 ms); at 12 MP (16 columns = whole lines) it removes a third of
+  // the middle's excess HBM reads (2.44 -> 2.28 GB against 1.91 GB asked for) but runs 3 % slower -- off there
+  pl.mid_swz = o.mid_swz >= 0 ? o.mid_swz : ((size_t)pl.T * sizeof(real2) < 128 && !g.slay ? 1 : 0);
+  // Measured (r03z_ab.log): at 12 MP (100-MB plane, 64-byte tile rows fetched as whole lines once per colour plane) the
+  // terms take 0.5 GB off the middle's HBM traffic, 0.622 -> 0.563 ms; on DiffuserCam-sized frames the 1-MB plane lives
+  // in the L2 and one load beats two (C1 middle 0.0206 -> 0.0221 ms with the terms)
+  pl.g_terms = o.g_plane >= 0 ? !o.g_plane : ((size_t)g.cplane * sizeof(real) > ((size_t)8 << 20));
+}
+
 // frame geometry (rfft_convolve.py:110-117) and the launch plan -- no device work (also serves lpc_plan_module)
-static int setup_shape(Engine* e, bool* want_static_out) {
+static int setup_shape(Engine* e, int cu, bool* want_static_out) {
   const lpc_config& c = e->cfg;
   PlaneGeom& g = e->g;
   g.H = c.height; g.W = c.width;
@@ -469,29 +536,29 @@ static int setup_shape(Engine* e, bool* want_static_out) {
     return fail("padded width " + std::to_string(g.Wp) + " > " + std::to_string(kMaxTilePoints) + " is not supported");
   // compile-time plans live in a plan module (lpc_plan.h): look for it, build it if allowed, else run-time plans
   const bool want_static = !e->opt.no_static && (long)g.Hp * g.Wp >= e->opt.jit_min_points;
-  choose_plan(e, want_static);
+  choose_plan(e, want_static, cu);
   *want_static_out = want_static;
   return 0;
 }
 
 static int setup_geometry(Engine* e) {
   bool want_static = false;
-  LPC_OK(setup_shape(e, &want_static));
+  const int cu = plan_cu_count();
+  LPC_OK(setup_shape(e, cu, &want_static));
   const lpc_config& c = e->cfg;
   const PlaneGeom& g = e->g;
   e->mod = nullptr;
   if (!want_static) e->mod_note = e->opt.no_static ? "no_static" : "small frame";
-  else if (e->spec.any()) {
-    e->mod = get_plan_module(e->spec, e->opt, e->opt.jit != 0, &e->mod_note);
+  else if (e->plan.spec.any()) {
+    e->mod = get_plan_module(e->plan.spec, e->opt, e->opt.jit != 0, &e->mod_note);
     if (!e->mod) {      // lpc_plan_info() names the module a deployment without a compiler would have to ship
-      const std::string key = plan_spec_key(e->spec);
+      const std::string key = plan_spec_key(e->plan.spec);
       if (e->mod_note.find(key) == std::string::npos) e->mod_note = "module " + key + ": " + e->mod_note;
-      choose_plan(e, false);
+      choose_plan(e, false, cu);
     }
   }
-  if (!e->mod) e->spec = PlanSpec{};
+  if (!e->mod) e->plan.spec = PlanSpec{};
   e->g.slay = (e->mod && e->mod->slay) ? 1 : 0;
-  const bool admm = c.algo == LPC_ALGO_ADMM;
   LPC_OK(build_plan(e, e->planW, g.Wp));
   e->rows_r2 = e->planW.nst >= 2 && e->planW.radix[e->planW.nst - 1] == 2;
   if (e->rows_r2) {
@@ -500,52 +567,27 @@ static int setup_geometry(Engine* e) {
     LPC_OK(plan_from_radices(e, e->planWi, g.Wp, rad));
     e->planWi.skew_ok = 0;
   }
-  if (e->rows_half) LPC_OK(build_plan(e, e->planWh, g.Wp / 2));
+  if (e->plan.rows_half) LPC_OK(build_plan(e, e->planWh, g.Wp / 2));
   e->tws_row = nullptr;
-  if (e->mod && e->spec.row_kind != LPC_ROWS_RUNTIME) LPC_OK(make_stage_twiddles(e, e->spec.row, &e->tws_row));
-  LPC_OK(build_plan(e, e->planB, e->N2));
-  if (e->N1 > 1) LPC_OK(build_plan(e, e->planA, e->N1));
-  // The half of the image-domain work that needs no neighbours rides in the module's forward row kernel: the blocks of
-  // `a` compute xi' and a = mu1 X - xi' from xi, HV, HV_old, y themselves (-2R per iteration), the tiled kernel keeps
-  // the stencil half at its own occupancy (without a module: the full stand-alone kernel) ...
-  e->xhalf_rows = admm && e->mod && e->mod->admm_rows_fwd_x;
-  // ... narrow frames (paired rows of one quad per lane: padded widths up to 1024) hand it the TV / W half too: three
-  // launches per iteration, r_sp never stored.  One small frame is a chain of launch boundaries and memory latencies
-  // (C1 -7.6 %), a batch saves the trip of r_sp through memory and the tiled kernel's launch (C4 -6.3 %);
-  // profiles/r05_notes.md section 5 (option k1_rows=0: off)
-  // (round 6: rows of TWO quads per lane as well -- padded widths up to 2048: the reference's own profile frame 760 x 1014
-  // gray 0.458 -> 0.442 ms per 5 iterations, 8 frames of 600 x 800 x 3 22.1 -> 20.8 ms per 20; profiles/r06_notes.md.  FOUR
-  // quads per lane -- 12-MP half-length rows -- are slower than the tiled kernel: not built)
-  e->k1_rows = e->xhalf_rows && g.Wp % 4 == 0 && e->mod->k1_rows != 0 && e->opt.k1_rows != 0;
-  // ... outside the sensor window that half works from HV alone (AdmmScalars::xiw; option xi_full: every pixel alike) ...
-  e->xi_window = e->xhalf_rows && !e->opt.xi_full;
-  // ... and rows wholly outside it skip the H V row transforms in both directions: the kept rows of SB are rescaled by
-  // forward pass A (any plan) or, for single-pass columns, by the module's fused middle (option hv_full: off)
-  e->hv_skip = e->xi_window && !e->opt.hv_full && e->mod->admm_rows_inv && (e->N1 > 1 || e->mod->admm_mid);
-  e->gd_fuse_fwd = c.algo >= LPC_ALGO_GD && e->mod && e->mod->gd_rows_update_fwd && !e->opt.gd_no_fuse_fwd;
-  // the second form of the fused row kernels: 8-byte accesses to y / x need an even window offset and frame width
-  e->gd_v2 = c.algo >= LPC_ALGO_GD && e->mod && e->mod->gd_v2 && e->tws_row && e->opt.gd_v2 != 0 &&
-             ((g.sw | g.W) & 1) == 0 && g.W >= 2;
-  if (e->opt.gd_rev < 0)     // EngineOpts::gd_rev
-    // all three (the row kernels and the register middle alternate with the forward-walking pass A, so every kernel
-    // starts where its predecessor finished): 12 MP FISTA 75.4 / 74.1 / 73.8 -> 74.5 / 73.0 / 72.8 ms per 40 iterations on
-    // three instances of one box against the middle alone (r03z_ab.log); no effect at 1080p, where nothing is reversed
-    e->opt.gd_rev = ((size_t)g.cplane * e->P * sizeof(real2) > ((size_t)200 << 20)) ? 7 : 0;
+  if (e->mod && e->plan.spec.row_kind != LPC_ROWS_RUNTIME) LPC_OK(make_stage_twiddles(e, e->plan.spec.row, &e->tws_row));
+  LPC_OK(build_plan(e, e->planB, e->plan.N2));
+  if (e->plan.N1 > 1) LPC_OK(build_plan(e, e->planA, e->plan.N1));
+  finish_plan(e, cu);
   LPC_OK(make_twiddles(e, g.Hp, &e->twH));
-  const int ntc = (g.Wc + e->T - 1) / e->T;
+  const int ntc = (g.Wc + e->plan.T - 1) / e->plan.T;
   ColPass& A = e->passA;
-  A.N = e->N1; A.G = e->N2; A.istride = e->N2; A.gstride = 1; A.T = e->T; A.ntile_c = ntc;
+  A.N = e->plan.N1; A.G = e->plan.N2; A.istride = e->plan.N2; A.gstride = 1; A.T = e->plan.T; A.ntile_c = ntc;
   A.tw_mode = 0; A.zr0 = 0; A.zr1 = g.Hp; A.twH = e->twH; A.need0 = 0; A.needn = g.Hp;
   A.sc_plane0 = INT_MAX; A.sc_r0 = 0; A.sc_r1 = g.Hp; A.sc = (real)1.;
-  A.tdiv = make_fastdiv((unsigned)e->T); A.tcdiv = make_fastdiv((unsigned)ntc);
+  A.tdiv = make_fastdiv((unsigned)e->plan.T); A.tcdiv = make_fastdiv((unsigned)ntc);
   A.swz = 0;
   A.rev = 0;
   A.ga = A.gb = nullptr;
   ColPass& B = e->passB;
   B = A;
-  B.N = e->N2; B.G = e->N1; B.istride = 1; B.gstride = e->N2;
-  if (e->spec.passA.n) {       // the module's pass A tiles the columns on its own (choose_plan)
-    A.T = e->spec.passA.T;
+  B.N = e->plan.N2; B.G = e->plan.N1; B.istride = 1; B.gstride = e->plan.N2;
+  if (e->plan.spec.passA.n) {       // the module's pass A tiles the columns on its own (choose_plan)
+    A.T = e->plan.spec.passA.T;
     A.ntile_c = (g.Wc + A.T - 1) / A.T;
     A.tdiv = make_fastdiv((unsigned)A.T);
     A.tcdiv = make_fastdiv((unsigned)A.ntile_c);
@@ -573,7 +615,7 @@ static int fft2_forward_setup(Engine* e, const RealSrc& src, real2* S, int nplan
   const PlaneGeom& g = e->g;
   const int zr0 = src.out_row0, zr1 = src.out_row0 + src.nrows;
   LPC_OK(rows_fwd_single(e, src, S, nplanes, -1));
-  if (e->N1 > 1) {
+  if (e->plan.N1 > 1) {
     LPC_OK(cols_passA(e, S, nplanes, false, zr0, zr1, -1));
     LPC_OK(cols_passB_fwd(e, S, nplanes, 0, g.Hp));
   } else {
@@ -648,10 +690,10 @@ static AdmmScalars admm_scalars(const Engine* e, const double cur[4]) {
   p.r_mu2p = (real)(1.0 / (double)p.mu2p); p.r_mu3p = (real)(1.0 / (double)p.mu3p);
   p.clamp_cur = e->vw_cur ? 1 : 0;
   p.clamp_old = e->vw_old ? 1 : 0;
-  p.xiw = e->xi_window ? 1 : 0;
+  p.xiw = e->plan.xi_window ? 1 : 0;
   p.xi_store = 1;              // admm_iterate clears it on all but the last iteration of a call
   p.skipa = p.skiphv = 0;      // set by admm_iterate inside a call (AdmmScalars::skipa)
-  p.rev = (e->opt.rev_order & 1) ? 1 : 0;
+  p.rev = e->plan.rev_k1 ? 1 : 0;
   p.half_in = p.half_out = 0;  // set by admm_iterate between the iterations of one call (AdmmScalars::half_in)
   return p;
 }
@@ -694,11 +736,7 @@ static int admm_split_gram(Engine* e) {
   if (g.slay)       // the 8-column middle reads the plane in pair lines
     LPC_OK(launch_k(e, -1, k_to_pair_lines<256, real>, grid1d((long)g.Hp * g.cpitch, 256), 256, 0, (const real*)e->Gabs,
                     e->Gabs_t, g.Hp, g.cpitch, g.cplane));
-  // Measured (r03z_ab.log): at 12 MP (100-MB plane, 64-byte tile rows fetched as whole lines once per colour plane) the
-  // terms take 0.5 GB off the middle's HBM traffic, 0.622 -> 0.563 ms; on DiffuserCam-sized frames the 1-MB plane lives
-  // in the L2 and one load beats two (C1 middle 0.0206 -> 0.0221 ms with the terms)
-  const int want = e->opt.g_plane >= 0 ? !e->opt.g_plane : ((size_t)g.cplane * sizeof(real) > ((size_t)8 << 20));
-  if (!want) return 0;
+  if (!e->plan.g_terms) return 0;
   const int n = (int)std::max<long>(g.Hp, g.cpitch);
   LPC_OK(launch_k(e, -1, k_gsep_extract, grid1d((long)n, 256), 256, 0, (const real*)e->Gabs, g.Hp, g.Wc,
                   (long)g.cpitch, e->Ga, e->Gb));
@@ -761,35 +799,35 @@ static int admm_reset(Engine* e) {
 // forward rows, [pass A], fused middle, [inverse pass A], inverse rows
 static int admm_spectral_step(Engine* e, const AdmmScalars& sc, real* Vout, real* HVout, bool xhalf = false,
                               const K1Rows* k1 = nullptr) {
-  if (xhalf) LPC_OK(admm_rows_fwd_x(e, sc, k1));
+  if (xhalf) LPC_OK(e->mod->admm_rows_fwd_x(e, &sc, k1));   // (LaunchPlan::xhalf_rows: the module holds it)
   else LPC_OK(admm_rows_fwd(e));
   LPC_OK(admm_cols(e, sc));
   return admm_rows_inv(e, Vout, HVout, sc.skiphv != 0);
 }
 
 
+// the image-domain kernel of a stand-alone K1 form (half_in: the duals arrive half-applied, AdmmScalars::half_in)
+typedef void (*K1Kernel)(PlaneGeom, AdmmScalars, const real*, const real*, const real*, const real*, real*, const real*,
+                         const real*, real*, real*, real*, const real*, real*, real*, unsigned);
+struct K1Launch { K1Kernel fn; int th, tw; size_t smem; };   // kernel, tile rows x columns, LDS bytes
+static K1Launch k1_launch(AdmmK1 form, bool half_in) {
+  constexpr int NT = 256, TW4 = 256;
+  auto smem4 = [](int th) { return (size_t)2 * (th + 2) * (TW4 + 8) * sizeof(real); };
+  switch (form) {
+    // the TV / W half alone (X half inside the forward rows) is lighter per pixel: 4-row tiles, one row per wave -- three
+    // alternations on one box (r02as): 0.940 -> 0.901 ms at 12 MP (6.03 TB/s), C4 0.641 -> 0.614 ms, C5 unchanged
+    case ADMM_K1_TV_W:
+      return half_in ? K1Launch{k_admm_spatial_v4<4, NT, false, true>, 4, TW4, smem4(4) / 2}
+                     : K1Launch{k_admm_spatial_v4<4, NT, false>, 4, TW4, smem4(4)};
+    case ADMM_K1_TILED: return {k_admm_spatial_v4<8, NT>, 8, TW4, smem4(8)};
+    default: return {k_admm_spatial<16, 64, NT>, 16, 64, (size_t)(2 * 18 * 66 + 17 * 64 + 16 * 65) * sizeof(real)};
+  }
+}
+
 static int admm_iterate(Engine* e, int n_iter) {
   const PlaneGeom& g = e->g;
-  constexpr int TH = 16, TW = 64, NT = 256;
-  const size_t k1_smem = (size_t)(2 * (TH + 2) * (TW + 2) + (TH + 1) * TW + TH * (TW + 1)) * sizeof(real);
-  const unsigned tiles_x = (g.Wp + TW - 1) / TW, tiles_y = (g.Hp + TH - 1) / TH;
-  const dim3 k1_grid(tiles_x * tiles_y, e->P, 1);
-  // 16-byte-lane kernel whenever the padded width allows aligned four-pixel lanes (every BASELINE size does)
-  const bool vec4 = g.Wp % 4 == 0;
-  constexpr int TH4 = 8, TW4 = 256;
-  const unsigned tiles_x4 = (g.Wp + TW4 - 1) / TW4, tiles_y4 = (g.Hp + TH4 - 1) / TH4;
-  const dim3 k1_grid4(tiles_x4 * tiles_y4, e->P, 1);
-  const size_t k1_smem4 = (size_t)2 * (TH4 + 2) * (TW4 + 8) * sizeof(real);
-  // the TV / W half alone (X half inside the forward rows) is lighter per pixel: 4-row tiles, one row per wave -- three
-  // alternations on one box (r02as): 0.940 -> 0.901 ms at 12 MP (6.03 TB/s), C4 0.641 -> 0.614 ms, C5 unchanged
-  constexpr int TH4X = 4;
-  const dim3 k1_grid4x(tiles_x4 * ((g.Hp + TH4X - 1) / TH4X), e->P, 1);
-  const size_t k1_smem4x = (size_t)2 * (TH4X + 2) * (TW4 + 8) * sizeof(real);
+  const LaunchPlan& pl = e->plan;
   bool sb_rows_valid = false;   // AdmmScalars::skipa may rely on the rows of SB only after a step of this very call
-  // K1Rows::xcd_order.  (The XCD-aware block orders assume the MI355X's 8 XCDs x 32 CUs and its dispatch rule "workgroup w
-  // on XCD w % 8"; any other part gets launch order: the orders are permutations, results are the same.)
-  const int k1_xcd_order = plan_cu_count() != 256 ? 0
-                           : (long)paired_rows_grid(g, false) * e->P <= 8192 ? -1 : std::max(0, e->opt.k1_group);
   for (int it = 0; it < n_iter; ++it) {
     real* Vc = e->V[e->vcur];
     real* Vo = e->V[e->vcur ^ 1];
@@ -801,45 +839,30 @@ static int admm_iterate(Engine* e, int n_iter) {
     // (sb_rows_valid: set below, local to the call -- no other entry point can have touched the work spectrum in
     // between); the last iteration runs complete (it stores xi out there), and the last three write H V there:
     // xi = mu1p (HV - HV_old) of the final X half and every read-out after the call need HV_{n-2}, HV_{n-1}, HV_n whole
-    sc.skipa = (e->hv_skip && sb_rows_valid && !sc.xi_store) ? 1 : 0;
-    sc.skiphv = (e->hv_skip && it + 3 < n_iter) ? 1 : 0;
-    // duals half-applied between the iterations of this call (AdmmScalars::half_in; option k1_half=0: never): the
-    // first iteration reads plain duals, the last one writes them -- nothing outside this loop sees the other form
-    const bool k1_half = vec4 && e->xhalf_rows && e->opt.k1_half != 0;
-    sc.half_in = (k1_half && it > 0) ? 1 : 0;
-    sc.half_out = (k1_half && it + 1 < n_iter) ? 1 : 0;
-    // small frames: the forward rows take the TV / W half as well (Engine::k1_rows) -- same buffers, same ping-pong
-    const bool k1r = e->k1_rows && vec4;
+    sc.skipa = (pl.hv_skip && sb_rows_valid && !sc.xi_store) ? 1 : 0;
+    sc.skiphv = (pl.hv_skip && it + 3 < n_iter) ? 1 : 0;
+    // duals half-applied between the iterations of this call (LaunchPlan::k1_half): the first iteration reads plain
+    // duals, the last one writes them -- nothing outside this loop sees the other form
+    sc.half_in = (pl.k1_half && it > 0) ? 1 : 0;
+    sc.half_out = (pl.k1_half && it + 1 < n_iter) ? 1 : 0;
+    // ADMM_K1_ROWS: the forward rows take the TV / W half as well -- same buffers, same ping-pong
     const K1Rows k1 = {Vc, Vo, e->eta0[e->ecur], e->eta1[e->ecur], e->eta0[e->ecur ^ 1], e->eta1[e->ecur ^ 1], e->rho,
-                       k1_xcd_order};
-    if (k1r) {
-    } else if (sc.half_in)
-      LPC_OK(launch_k(e, LPC_K_SPATIAL, k_admm_spatial_v4<TH4X, NT, false, true>, k1_grid4x, NT, k1_smem4x / 2, g, sc, (const real*)Vc,
-                      (const real*)Vo, (const real*)e->HVb[e->hcur], (const real*)e->HVb[e->hcur ^ 1], e->xi, (const real*)e->eta0[e->ecur],
-                      (const real*)e->eta1[e->ecur], e->eta0[e->ecur ^ 1], e->eta1[e->ecur ^ 1], e->rho,
-                      (const real*)e->Y, e->Rsp, e->Aarr, tiles_x4));
-    else if (vec4 && e->xhalf_rows)
-      LPC_OK(launch_k(e, LPC_K_SPATIAL, k_admm_spatial_v4<TH4X, NT, false>, k1_grid4x, NT, k1_smem4x, g, sc, (const real*)Vc,
-                      (const real*)Vo, (const real*)e->HVb[e->hcur], (const real*)e->HVb[e->hcur ^ 1], e->xi, (const real*)e->eta0[e->ecur],
-                      (const real*)e->eta1[e->ecur], e->eta0[e->ecur ^ 1], e->eta1[e->ecur ^ 1], e->rho,
-                      (const real*)e->Y, e->Rsp, e->Aarr, tiles_x4));
-    else if (vec4)
-      LPC_OK(launch_k(e, LPC_K_SPATIAL, k_admm_spatial_v4<TH4, NT>, k1_grid4, NT, k1_smem4, g, sc, (const real*)Vc,
-                      (const real*)Vo, (const real*)e->HVb[e->hcur], (const real*)e->HVb[e->hcur ^ 1], e->xi, (const real*)e->eta0[e->ecur],
-                      (const real*)e->eta1[e->ecur], e->eta0[e->ecur ^ 1], e->eta1[e->ecur ^ 1], e->rho,
-                      (const real*)e->Y, e->Rsp, e->Aarr, tiles_x4));
-    else
-    LPC_OK(launch_k(e, LPC_K_SPATIAL, k_admm_spatial<TH, TW, NT>, k1_grid, NT, k1_smem, g, sc, (const real*)Vc,
-                    (const real*)Vo, (const real*)e->HVb[e->hcur], (const real*)e->HVb[e->hcur ^ 1], e->xi, (const real*)e->eta0[e->ecur],
-                    (const real*)e->eta1[e->ecur], e->eta0[e->ecur ^ 1], e->eta1[e->ecur ^ 1], e->rho,
-                    (const real*)e->Y, e->Rsp, e->Aarr, tiles_x));
+                       pl.k1_xcd_order};
+    if (pl.k1 != ADMM_K1_ROWS) {
+      const K1Launch k = k1_launch(pl.k1, sc.half_in != 0);
+      const unsigned tiles_x = (g.Wp + k.tw - 1) / k.tw, tiles_y = (g.Hp + k.th - 1) / k.th;
+      LPC_OK(launch_k(e, LPC_K_SPATIAL, k.fn, dim3(tiles_x * tiles_y, e->P, 1), 256, k.smem, g, sc, (const real*)Vc,
+                      (const real*)Vo, (const real*)e->HVb[e->hcur], (const real*)e->HVb[e->hcur ^ 1], e->xi,
+                      (const real*)e->eta0[e->ecur], (const real*)e->eta1[e->ecur], e->eta0[e->ecur ^ 1],
+                      e->eta1[e->ecur ^ 1], e->rho, (const real*)e->Y, e->Rsp, e->Aarr, tiles_x));
+    }
     e->vw_old = e->vw_cur;          // this iteration's "V as W saw it" becomes the next one's "V_old as W_old saw it"
     e->vw_cur = false;
     e->ecur ^= 1;
     e->first = false;
     // (hcur still names the CURRENT H V here: the X half inside the forward rows reads HVb[hcur] and HVb[hcur ^ 1]
     // before the inverse rows of this same step overwrite HVb[hcur ^ 1] -- stream order)
-    LPC_OK(admm_spectral_step(e, sc, Vo, e->HVb[e->hcur ^ 1], vec4 && e->xhalf_rows, k1r ? &k1 : nullptr));
+    LPC_OK(admm_spectral_step(e, sc, Vo, e->HVb[e->hcur ^ 1], pl.xhalf_rows, pl.k1 == ADMM_K1_ROWS ? &k1 : nullptr));
     e->vcur ^= 1;  // Vo now holds the new image estimate
     e->hcur ^= 1;  // ... and the other H V buffer its forward model
     sb_rows_valid = true;   // the inverse column passes of this step left rfft(H V row) / Wp in every row of SB
@@ -915,12 +938,12 @@ int lpc_plan_module(const lpc_config* cfg, int build, char* key_buf, size_t n) {
   std::string err = parse_all_opts(cfg->options, tmp.opt);
   if (!err.empty()) return fail("lpc_plan_module: " + err);
   bool want_static = false;
-  LPC_OK(setup_shape(&tmp, &want_static));
-  const bool any = want_static && tmp.spec.any();
-  if (key_buf && n) std::snprintf(key_buf, n, "%s", any ? plan_spec_key(tmp.spec).c_str() : "");
+  LPC_OK(setup_shape(&tmp, plan_cu_count(), &want_static));
+  const bool any = want_static && tmp.plan.spec.any();
+  if (key_buf && n) std::snprintf(key_buf, n, "%s", any ? plan_spec_key(tmp.plan.spec).c_str() : "");
   if (!any || !build) return 0;
   std::string path;
-  if (build_plan_module(tmp.spec, tmp.opt, &path) != 0) return fail(path);
+  if (build_plan_module(tmp.plan.spec, tmp.opt, &path) != 0) return fail(path);
   return 0;
 }
 
@@ -1022,7 +1045,7 @@ int lpc_convolve_spectrum(lpc_handle e, const real* dev_x, real* dev_out, int n,
     LPC_OK(fft2_forward_setup(e, src_unpadded(e, xin), e->S, nplanes));
   }
   return launch_k(e, -1, k_spectrum_mul_to_hwc<256>, grid1d((long)g.Hp * g.Wc * g.C, 256, nimg), 256, 0, g,
-                  (const real2*)e->S, (const real2*)e->Hs, adjoint ? 1 : 0, (real2*)dev_out, e->N1, e->N2);
+                  (const real2*)e->S, (const real2*)e->Hs, adjoint ? 1 : 0, (real2*)dev_out, e->plan.N1, e->plan.N2);
 }
 
 int lpc_set_data(lpc_handle e, const real* dev_data, int data_channels, void* stream) {
@@ -1212,7 +1235,7 @@ int lpc_set_psi_gram(lpc_handle e, const real* dev_gabs, void* stream) {
   const PlaneGeom& g = e->g;
   LPC_RT(rt::memset_async(e->Gabs, 0, (size_t)g.cplane * sizeof(real), e->stream));
   LPC_OK(launch_k(e, -1, k_permute_spectrum_rows<256>, grid1d((long)g.Hp * g.Wc, 256), 256, 0, dev_gabs, e->Gabs, g.Hp,
-                  g.Wc, g.cpitch, e->N1, e->N2));
+                  g.Wc, g.cpitch, e->plan.N1, e->plan.N2));
   return admm_split_gram(e);
 }
 
@@ -1531,12 +1554,13 @@ int lpc_profile_read(lpc_handle e, double* avg_ms, long* launches) {
 int lpc_kernel_bytes(lpc_handle e, int kid, double* bytes) {
   if (!e || !bytes) return fail("null argument");
   const PlaneGeom& g = e->g;
+  const LaunchPlan& pl = e->plan;
   const double eb = (double)sizeof(real);             // 4 (liblpc) or 8 (liblpc_f64)
   const double R = eb * g.Hp * g.Wp * e->P;           // padded real arrays, all planes
   const double S = 2 * eb * g.Hp * g.Wc * e->P;       // half spectra
   const double R0 = eb * g.H * g.W * e->Pdata;
   const double Sc = 2 * eb * g.Hp * g.Wc * e->Ppsf;   // spectral constants
-  const bool split = e->N1 > 1;
+  const bool split = pl.N1 > 1, k1_rows = pl.k1 == ADMM_K1_ROWS;
   const double fr = (double)g.H / (double)g.Hp;
   double b = 0.0;
   if (e->cfg.algo == LPC_ALGO_ADMM) {
@@ -1550,20 +1574,19 @@ int lpc_kernel_bytes(lpc_handle e, int kid, double* bytes) {
       // ... and without V_old once the duals travel half-applied between the iterations of a call (k1_half): 8R
       // ... k1_rows (small frames): not launched; the forward rows read V, eta0, eta1, rho (+ V_old without k1_half)
       // instead of r_sp and write eta0, eta1, rho: + 6R (7R)
-      case LPC_K_SPATIAL: b = e->k1_rows ? 0.0 : e->xhalf_rows ? ((e->opt.k1_half != 0 && g.Wp % 4 == 0) ? 8.0 : 9.0) * R
-                                            : 15.0 * R + R0; break;
+      case LPC_K_SPATIAL: b = k1_rows ? 0.0 : pl.xhalf_rows ? (pl.k1_half ? 8.0 : 9.0) * R : 15.0 * R + R0; break;
       // ... with xi confined to the sensor window (AdmmScalars::xiw) the row kernel reads r_sp, HV everywhere (2R) and
       // xi, HV_old / writes xi only over the window (3 window-sized arrays per plane) and y: 2R + 3 Rw + R0 + 2S
       // ... and with the H V row transforms skipped on rows wholly outside the window (AdmmScalars::skipa, steady state
       // of a long call; fr = H / Hp): rows fwd (1 + fr) R + 3 Rw + R0 + (1 + fr) S, rows inv (1 + fr) (S + R)
-      case LPC_K_ROW_FWD: b = (e->hv_skip ? (1.0 + fr) * R + 3.0 * eb * g.H * g.W * e->P + R0 + (1.0 + fr) * S
-                                  : e->xi_window ? 2.0 * R + 3.0 * eb * g.H * g.W * e->P + R0 + 2.0 * S
-                                  : e->xhalf_rows ? 5.0 * R + R0 + 2.0 * S : 2.0 * R + 2.0 * S)
-                                 + (e->k1_rows ? (e->opt.k1_half != 0 ? 6.0 : 7.0) * R : 0.0); break;
+      case LPC_K_ROW_FWD: b = (pl.hv_skip ? (1.0 + fr) * R + 3.0 * eb * g.H * g.W * e->P + R0 + (1.0 + fr) * S
+                                  : pl.xi_window ? 2.0 * R + 3.0 * eb * g.H * g.W * e->P + R0 + 2.0 * S
+                                  : pl.xhalf_rows ? 5.0 * R + R0 + 2.0 * S : 2.0 * R + 2.0 * S)
+                                 + (k1_rows ? (pl.k1_half ? 6.0 : 7.0) * R : 0.0); break;
       case LPC_K_COL_A_FWD: b = split ? 4.0 * S : 0.0; break;
       case LPC_K_COL_MID: b = 4.0 * S + Sc + (e->g_sep ? 0. : eb * g.Hp * g.Wc); break;  // + H (complex) + |G| (real, one plane; two vectors when it separates)
       case LPC_K_COL_A_INV: b = split ? 4.0 * S : 0.0; break;
-      case LPC_K_ROW_INV: b = e->hv_skip ? (1.0 + fr) * (S + R) : 2.0 * S + 2.0 * R; break;
+      case LPC_K_ROW_INV: b = pl.hv_skip ? (1.0 + fr) * (S + R) : 2.0 * S + 2.0 * R; break;
       default: return fail("bad kernel id");
     }
   } else if (e->cfg.algo >= LPC_ALGO_GD) {
@@ -1578,28 +1601,23 @@ int lpc_kernel_bytes(lpc_handle e, int kid, double* bytes) {
 int lpc_plan_info(lpc_handle e, char* buf, size_t n) {
   if (!e || !buf || n == 0) return fail("null argument");
   const PlaneGeom& g = e->g;
-  const PlanSpec& sp = e->spec;
-  auto radstr = [](const StaticFft& f) {
-    std::string r;
-    for (int i = 0; i < f.nst; ++i) r += (i ? "." : "") + std::to_string(f.rad[i]);
-    return r;
-  };
+  const LaunchPlan& pl = e->plan;
+  const PlanSpec& sp = pl.spec;
   std::string s = "padded " + std::to_string(g.Hp) + "x" + std::to_string(g.Wp);
-  s += e->rows_half ? "; rows: half-length " + std::to_string(g.Wp / 2) : "; rows: paired " + std::to_string(g.Wp);
-  const bool rows_static = e->mod && sp.row_kind && (e->rows_half || e->cfg.algo == LPC_ALGO_ADMM);
-  if (rows_static) s += " [static " + radstr(sp.row) + ", " + std::to_string(sp.row.nt) + " threads]";
-  if (e->gd_v2) s += " (fused rows: second form, " + std::to_string(sp.row.n / sp.row.rad[0]) + " lanes)";
-  s += "; columns: " + (e->N1 > 1 ? std::to_string(e->N1) + " x " + std::to_string(e->N2) + " split" : std::string("single pass ") + std::to_string(e->N2));
-  s += ", T = " + std::to_string(e->T);
-  if (e->mod && sp.passA.n) s += ", pass A [static " + radstr(sp.passA) + ", T = " + std::to_string(sp.passA.T) + "]";
+  s += pl.rows_half ? "; rows: half-length " + std::to_string(g.Wp / 2) : "; rows: paired " + std::to_string(g.Wp);
+  const bool rows_static = e->mod && sp.row_kind && (pl.rows_half || e->cfg.algo == LPC_ALGO_ADMM);
+  if (rows_static) s += " [static " + rad_list(sp.row, ".") + ", " + std::to_string(sp.row.nt) + " threads]";
+  if (pl.gd_v2) s += " (fused rows: second form, " + std::to_string(sp.row.n / sp.row.rad[0]) + " lanes)";
+  s += "; columns: " + (pl.N1 > 1 ? std::to_string(pl.N1) + " x " + std::to_string(pl.N2) + " split" : std::string("single pass ") + std::to_string(pl.N2));
+  s += ", T = " + std::to_string(pl.T);
+  if (e->mod && sp.passA.n) s += ", pass A [static " + rad_list(sp.passA, ".") + ", T = " + std::to_string(sp.passA.T) + "]";
   if (e->cfg.algo == LPC_ALGO_ADMM) {
-    const bool reg = e->N1 > 1 && e->mid_reg && sizeof(real) == 4 && e->N2 == 24;
-    s += reg ? ", middle in registers"
-             : (e->mod && sp.mid_kind ? ", LDS middle [static " + radstr(sp.mid) + (sp.mid_kind == LPC_MID_SEQ ? ", one spectrum at a time" : "") + (g.slay ? ", pair-line spectra]" : "]")
-                                      : ", LDS middle");
-    s += e->k1_rows ? "; TV / W half and X half inside the forward rows (three launches per iteration)"
-         : e->xhalf_rows ? "; tiled TV / W kernel + X half inside the forward rows" : "; stand-alone image-domain kernel";
-    if (e->xi_window) s += e->hv_skip ? " (xi inside the sensor window only, H V row transforms skipped outside it)"
+    s += pl.admm_mid == ADMM_MID_REG24 ? ", middle in registers"
+         : pl.admm_mid == ADMM_MID_MODULE ? ", LDS middle [static " + rad_list(sp.mid, ".") + (sp.mid_kind == LPC_MID_SEQ ? ", one spectrum at a time" : "") + (g.slay ? ", pair-line spectra]" : "]")
+                                          : ", LDS middle";
+    s += pl.k1 == ADMM_K1_ROWS ? "; TV / W half and X half inside the forward rows (three launches per iteration)"
+         : pl.k1 == ADMM_K1_TV_W ? "; tiled TV / W kernel + X half inside the forward rows" : "; stand-alone image-domain kernel";
+    if (pl.xi_window) s += pl.hv_skip ? " (xi inside the sensor window only, H V row transforms skipped outside it)"
                                       : " (xi inside the sensor window only)";
   }
   if (e->cfg.algo == LPC_ALGO_ADMM && e->g_sep) s += "; gram as row + column terms";

@@ -79,24 +79,49 @@ struct KernelTimer {
   unsigned mask = ~0u;      // bit k: launches of kernel id k are bracketed (lpc_profile_enable)
 };
 
+// ADMM image-domain kernel (K1): inside the forward rows (TV / W half and X half: three launches per iteration); tiled
+// TV / W half with the X half inside the forward rows; stand-alone on 16-byte lanes (padded width a multiple of 4) or scalar
+enum AdmmK1 { ADMM_K1_ROWS, ADMM_K1_TV_W, ADMM_K1_TILED, ADMM_K1_SCALAR };
+// ADMM fused middle: 24-point pass B in registers; the plan module's LDS middle; run-time plan in LDS on 512 threads x 18
+// points, or on the workgroup shape of its tile size
+enum AdmmMid { ADMM_MID_REG24, ADMM_MID_MODULE, ADMM_MID_RT_512X18, ADMM_MID_RT_LDS };
+
+// The launch plan of a handle: every kernel, tile shape, block order and fusion it runs, decided once at lpc_create
+// (lpc_engine.cpp: choose_plan, finish_plan).  The launch code reads this record and nothing else of the options.
+struct LaunchPlan {
+  // -- choose_plan: what the plan module's key needs
+  PlanSpec spec;           // the compile-time-plan kernels this handle runs (lpc_plan.h)
+  int N1 = 1, N2 = 1;      // column split Hp = N1*N2 (N1 == 1: single pass)
+  int T = 16;              // image columns per column-pass tile
+  bool rows_half = false;  // one real row per half-length transform
+  // -- finish_plan: once the module is loaded or refused
+  bool xhalf_rows = false; // ADMM: xi / a = mu1 X - xi computed by the forward row kernel of the module
+  bool xi_window = false;  // ... which then skips xi / HV_old outside the sensor window (AdmmScalars::xiw)
+  bool hv_skip = false;    // ... and rows wholly outside it skip the H V row transforms in both directions (AdmmScalars::skipa)
+  AdmmK1 k1 = ADMM_K1_SCALAR;
+  bool k1_half = false;    // duals half-applied between the iterations of one call (AdmmScalars::half_in)
+  int k1_xcd_order = 0;    // K1Rows::xcd_order
+  AdmmMid admm_mid = ADMM_MID_RT_LDS;
+  int conv_mid_reg = 0;    // convolution middle (conv_middle) in registers: its pass-B length; 0: in LDS
+  bool gd_fuse_fwd = false;   // gradient-descent family: update kernel + next forward rows in one launch
+  bool gd_v2 = false;         // ... its two fused row kernels in their second form (lpc_gd_v2_kernels.h; option gd_v2)
+  // block orders, backwards (EngineOpts::rev_order, gd_rev): permutations, results unchanged
+  bool rev_k1 = false, rev_passa_fwd = false, rev_passa_inv = false, rev_mid = false;
+  bool gd_rev_resid = false, gd_rev_update = false, gd_rev_mid = false;
+  int mid_swz = 0;         // ColPass::swz of the ADMM middle
+  bool g_terms = false;    // ADMM middles read |PsiT Psi| as row + column terms when it separates (EngineOpts::g_plane)
+};
+
 struct lpc_engine {
   lpc_config cfg{};
   PlaneGeom g{};
-  int N1 = 1, N2 = 1;  // column split Hp = N1*N2 (N1 == 1: single pass)
-  int T = 16;          // image columns per column-pass tile
   Fft1dPlan planW{}, planA{}, planB{};
   Fft1dPlan planWi{};   // inverse-row plan with the radix-2 stage FIRST (rows_r2 only)
   Fft1dPlan planWh{};   // length Wp/2: ADMM rows, one real row per half-length transform (rows_half)
-  bool rows_half = false;
-  EngineOpts opt;          // lpc_config::options
-  PlanSpec spec;           // the compile-time-plan kernels this handle runs (lpc_plan.h) ...
-  const struct LpcModule* mod = nullptr;   // ... and the loaded plan module that holds them (null: run-time plans only)
+  EngineOpts opt;          // lpc_config::options, as parsed (read by the plan functions and lpc_jit.cpp only)
+  LaunchPlan plan;
+  const struct LpcModule* mod = nullptr;   // the loaded plan module that holds plan.spec's kernels (null: run-time plans only)
   std::string mod_note;    // why there is no module, for lpc_plan_info
-  bool xhalf_rows = false; // ADMM: xi / a = mu1 X - xi computed by the forward row kernel of the module
-  bool k1_rows = false;    // ... and the TV / W half too: three launches per iteration (small frames, option k1_rows)
-  bool xi_window = false;  // ... which then skips xi / HV_old outside the sensor window (AdmmScalars::xiw)
-  bool hv_skip = false;    // ... and rows wholly outside it skip the H V row transforms in both directions (AdmmScalars::skipa)
-  bool mid_reg = true;  // register-resident fused middle where the pass-B length allows (option mid_lds=1: off)
   bool rows_r2 = false; // row plans end in a radix-2 stage: fold it into the Hermitian (un)tangling
   ColPass passA{}, passB{};
   int P = 0, Ppsf = 0, Pdata = 0;
@@ -153,8 +178,6 @@ struct lpc_engine {
   real* psf_planar = nullptr;
   bool has_init = false, psf_set = false, data_set = false, first = true;
   bool gd_fwd_done = false;    // the row spectra of H x's input are already in S (written by the fused update kernel)
-  bool gd_fuse_fwd = false;    // gradient-descent family: update kernel + next forward rows in one launch
-  bool gd_v2 = false;          // ... its two fused row kernels in their second form (lpc_gd_v2_kernels.h; option gd_v2)
   bool split_pending = false;  // lpc_iterate_begin ran, lpc_iterate_end has not yet
   // plug-and-play ADMM (lpc_admm_pnp_begin / _end): explicit state in the arrays the fused path uses for the TV duals
   //   eta0[0] = eta, eta1[0] = U, eta0[1] = X, eta1[1] = W   (all image-shaped)
@@ -274,7 +297,6 @@ int build_plan_module(const PlanSpec& spec, const EngineOpts& opt, std::string* 
 int rows_fwd_single(Engine* e, const RealSrc& src, real2* S, int nplanes, int kid);
 int rows_inv_single(Engine* e, const real2* S, const RealDst& dst, int nplanes, int kid);
 int admm_rows_fwd(Engine* e);                                   // e->Rsp, e->Aarr -> the two work spectra
-int admm_rows_fwd_x(Engine* e, const AdmmScalars& sc, const K1Rows* k1 = nullptr);          // e->Rsp and (xi, HV, HV_old, y) -> the two work spectra
 int admm_rows_inv(Engine* e, real* Vout, real* HVout, bool skip_hv_outside = false);          // the two work spectra -> V, H V
 // lpc_cols.cpp
 int cols_passA(Engine* e, real2* S, int nplanes, bool inverse, int zr0, int zr1, int kid, bool crop_rows_only = false,
@@ -285,4 +307,3 @@ int admm_cols(Engine* e, const AdmmScalars& sc);   // sc.skipa: forward pass A r
 // lpc_gd.cpp, lpc_gd_update.cpp, lpc_gd_update_fwd.cpp (one kernel family each)
 int gd_rows_mid(Engine* e);                                     // irfft rows -> residual -> rfft rows (S -> S2)
 int gd_rows_update(Engine* e, const GdScalars& sc, const real* alpha);   // irfft rows -> fused projected update
-int gd_rows_update_fwd(Engine* e, const GdScalars& sc, const real* alpha);   // ... -> next iteration's forward rows (S)

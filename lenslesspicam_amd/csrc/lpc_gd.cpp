@@ -7,7 +7,7 @@ int gd_rows_mid(Engine* e) {
   const PlaneGeom& g = e->g;
   const int nblk = (g.H + 1) / 2;
   if (e->mod && e->mod->gd_rows_mid) return e->mod->gd_rows_mid(e);
-  if (e->rows_half)
+  if (e->plan.rows_half)
     return dispatch_row(g.Wp / 2, e->planWh.skew_ok, false, [&](auto NTc, auto EM, auto SK, auto) {
       constexpr int nt = decltype(NTc)::value, em = decltype(EM)::value;
       constexpr bool sk = decltype(SK)::value;

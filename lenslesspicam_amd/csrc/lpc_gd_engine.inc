@@ -88,8 +88,8 @@ static int gd_iterate(Engine* e, int n_iter, int split = 0) {
       sc.first = 0;
       alpha = e->galpha_sched + i * e->cfg.channels;
     }
-    if (e->gd_fuse_fwd && !split) {
-      LPC_OK(gd_rows_update_fwd(e, sc, alpha));
+    if (e->plan.gd_fuse_fwd && !split) {
+      LPC_OK(e->mod->gd_rows_update_fwd(e, &sc, alpha));   // (LaunchPlan::gd_fuse_fwd: the module holds it)
       e->gd_fwd_done = true;
     } else {
       LPC_OK(gd_rows_update(e, sc, alpha));
@@ -133,12 +133,12 @@ static int gd_kernel_bytes(Engine* e, int kid, double* bytes) {
   const double S = 2 * eb * g.Hp * g.Wc * e->P;
   const double R0 = eb * g.H * g.W * e->P;
   const double Sc = 2 * eb * g.Hp * g.Wc * e->Ppsf;
-  const bool split = e->N1 > 1;
+  const bool split = e->plan.N1 > 1;
   const int kind = e->cfg.algo - LPC_ALGO_GD;
   double b = 0.0;
   switch (kid) {
     // update: gradient rows + x (+aux) read / write (+ the next iteration's row spectra when its forward rows are fused in)
-    case LPC_K_SPATIAL: b = f * S + (kind == 0 ? 2.0 : 4.0) * R0 + (e->gd_fuse_fwd ? f * S : 0.0); break;
+    case LPC_K_SPATIAL: b = f * S + (kind == 0 ? 2.0 : 4.0) * R0 + (e->plan.gd_fuse_fwd ? f * S : 0.0); break;
     case LPC_K_ROW_FWD: b = R0 + f * S; break;
     case LPC_K_COL_A_FWD: b = split ? (f * S + S) : 0.0; break;
     case LPC_K_COL_MID: b = (split ? 2.0 * S : (f * S + S)) + Sc; break;

@@ -13,7 +13,7 @@ int gd_rows_update_paired_plain(Engine* e, const GdScalars& sc, const real* alph
 int gd_rows_update(Engine* e, const GdScalars& sc, const real* alpha) {
   const PlaneGeom& g = e->g;
   if (e->mod && e->mod->gd_rows_update) return e->mod->gd_rows_update(e, &sc, alpha);
-  if (e->rows_half)
+  if (e->plan.rows_half)
     return dispatch_row(g.Wp / 2, e->planWh.skew_ok, false, [&](auto NTc, auto EM, auto SK, auto) {
       constexpr int nt = decltype(NTc)::value, em = decltype(EM)::value;
       constexpr bool sk = decltype(SK)::value;
@@ -22,10 +22,4 @@ int gd_rows_update(Engine* e, const GdScalars& sc, const real* alpha) {
                       e->gaux, alpha, sc);
     });
   return e->rows_r2 ? gd_rows_update_paired_r2(e, sc, alpha) : gd_rows_update_paired_plain(e, sc, alpha);
-}
-
-// the same + the forward row transform of the updated rows (e->S2 -> x, e->S): compile-time half-row plans only
-int gd_rows_update_fwd(Engine* e, const GdScalars& sc, const real* alpha) {
-  if (e->mod && e->mod->gd_rows_update_fwd) return e->mod->gd_rows_update_fwd(e, &sc, alpha);
-  return fail("internal: the update kernel with fused forward rows lives in the plan module");
 }

@@ -93,29 +93,29 @@ static int m_gd_rows_mid(Engine* e) {
   const PlaneGeom& g = e->g;
 #ifndef LPC_DOUBLE
   if constexpr (GdV2<RowP>::ok) {
-    if (e->gd_v2)     // second form (lpc_gd_v2_kernels.h): one-radix plan, M / R lanes per row
+    if (e->plan.gd_v2)     // second form (lpc_gd_v2_kernels.h): one-radix plan, M / R lanes per row
       return launch_k(e, LPC_K_ROW_INV, k_gd_resid_v2<GdV2<RowP>::NB, V2SK, RowPA>, dim3(g.H, e->P), GdV2<RowP>::NB, kV2Smem,
-                      geom_rev(e, e->opt.gd_rev & 1), row_arg(e), e->planW.tw, (const real2*)e->S, e->S2,
+                      geom_rev(e, e->plan.gd_rev_resid), row_arg(e), e->planW.tw, (const real2*)e->S, e->S2,
                       (const real*)e->Y, make_fastdiv((unsigned)g.DC), make_fastdiv((unsigned)g.C));
   }
 #endif
   return launch_k(e, LPC_K_ROW_INV, k_rinv_gd_mid_half<RNT, REM, RSK, RowPA>, dim3(g.H, e->P), RNT, kRowSmem,
-                  geom_rev(e, e->opt.gd_rev & 1),
+                  geom_rev(e, e->plan.gd_rev_resid),
                   row_arg(e), e->planW.tw, (const real2*)e->S, e->S2, (const real*)e->Y);
 }
 static int m_gd_rows_update(Engine* e, const GdScalars* sc, const real* alpha) {
   const PlaneGeom& g = e->g;
   return launch_k(e, LPC_K_SPATIAL, k_rinv_gd_update_half<RNT, REM, RSK, RowPA>, dim3(g.H, e->P), RNT, kRowSmem,
-                  geom_rev(e, e->opt.gd_rev & 2),
+                  geom_rev(e, e->plan.gd_rev_update),
                   row_arg(e), e->planW.tw, (const real2*)e->S2, e->gx, e->gaux, alpha, *sc);
 }
 static int m_gd_rows_update_fwd(Engine* e, const GdScalars* sc, const real* alpha) {
   const PlaneGeom& g = e->g;
 #ifndef LPC_DOUBLE
   if constexpr (GdV2<RowP>::ok) {
-    if (e->gd_v2) {
+    if (e->plan.gd_v2) {
       auto go = [&](auto kernel) {
-        return launch_k(e, LPC_K_SPATIAL, kernel, dim3(g.H, e->P), GdV2<RowP>::NB, kV2Smem, geom_rev(e, e->opt.gd_rev & 2),
+        return launch_k(e, LPC_K_SPATIAL, kernel, dim3(g.H, e->P), GdV2<RowP>::NB, kV2Smem, geom_rev(e, e->plan.gd_rev_update),
                         row_arg(e), e->planW.tw, (const real2*)e->S2, e->S, e->gx, e->gaux, alpha, *sc,
                         make_fastdiv((unsigned)g.C));
       };
@@ -127,7 +127,7 @@ static int m_gd_rows_update_fwd(Engine* e, const GdScalars* sc, const real* alph
   }
 #endif
   return launch_k(e, LPC_K_SPATIAL, k_rinv_gd_update_fwd_half<RNT, REM, RSK, RowPA>, dim3(g.H, e->P), RNT, kRowSmem,
-                  geom_rev(e, e->opt.gd_rev & 2),
+                  geom_rev(e, e->plan.gd_rev_update),
                   row_arg(e), e->planW.tw, (const real2*)e->S2, e->S, e->gx, e->gaux, alpha, *sc);
 }
 #endif

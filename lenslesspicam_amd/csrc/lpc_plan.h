@@ -70,9 +70,9 @@ static inline std::string plan_spec_key(const PlanSpec& s) {
   if (s.mid_kind) k += std::string(s.mid_kind == LPC_MID_PAIR ? "_mp" : "_ms") + fft_key(s.mid) + "m" + std::to_string(s.mid_minw) + (s.mid_pre ? "p" : "") + (s.slay ? "L" : "") + (s.mid_pc == 1 ? "c" : (s.mid_pc == 2 ? "r" : ""));
   return k;
 }
-static inline std::string rad_list(const StaticFft& f) {
+static inline std::string rad_list(const StaticFft& f, const char* sep = ",") {
   std::string s;
-  for (int i = 0; i < f.nst; ++i) s += (i ? "," : "") + std::to_string(f.rad[i]);
+  for (int i = 0; i < f.nst; ++i) s += (i ? sep : "") + std::to_string(f.rad[i]);
   return s;
 }
 // the -D flags lpc_module.cpp is compiled with

@@ -6,7 +6,7 @@
 int rows_fwd_single(Engine* e, const RealSrc& src, real2* S, int nplanes, int kid) {
   const PlaneGeom& g = e->g;
   if (e->mod && e->mod->rows_fwd_single) return e->mod->rows_fwd_single(e, &src, S, nplanes, kid);
-  if (e->rows_half)
+  if (e->plan.rows_half)
     return dispatch_row(g.Wp / 2, e->planWh.skew_ok, false, [&](auto NT, auto EM, auto SK, auto) {
       constexpr int nt = decltype(NT)::value, em = decltype(EM)::value;
       constexpr bool sk = decltype(SK)::value;
@@ -25,7 +25,7 @@ int rows_fwd_single(Engine* e, const RealSrc& src, real2* S, int nplanes, int ki
 int rows_inv_single(Engine* e, const real2* S, const RealDst& dst, int nplanes, int kid) {
   const PlaneGeom& g = e->g;
   if (e->mod && e->mod->rows_inv_single) return e->mod->rows_inv_single(e, S, &dst, nplanes, kid);
-  if (e->rows_half)
+  if (e->plan.rows_half)
     return dispatch_row(g.Wp / 2, e->planWh.skew_ok, false, [&](auto NT, auto EM, auto SK, auto) {
       constexpr int nt = decltype(NT)::value, em = decltype(EM)::value;
       constexpr bool sk = decltype(SK)::value;
@@ -48,7 +48,7 @@ int admm_rows_fwd(Engine* e) {
   real2* SA = e->S;
   real2* SB = e->S + (size_t)e->P * g.cplane;
   if (e->mod && e->mod->admm_rows_fwd) return e->mod->admm_rows_fwd(e);
-  if (e->rows_half)
+  if (e->plan.rows_half)
     return dispatch_row(g.Wp / 2, e->planWh.skew_ok, false, [&](auto NTc, auto EM, auto SK, auto) {
       constexpr int nt = decltype(NTc)::value, em = decltype(EM)::value;
       constexpr bool sk = decltype(SK)::value;
@@ -64,13 +64,6 @@ int admm_rows_fwd(Engine* e) {
   });
 }
 
-// ---- ADMM: forward rows of r_sp (stored) and of a = mu1 X - xi' (computed in the kernel from xi, HV, HV_old, y) ------
-// compile-time plans only: k_rfwd_half_x (half-length rows) / k_rfwd_arrays_x (paired rows)
-int admm_rows_fwd_x(Engine* e, const AdmmScalars& sc, const K1Rows* k1) {
-  if (e->mod && e->mod->admm_rows_fwd_x) return e->mod->admm_rows_fwd_x(e, &sc, k1);
-  return fail("internal: the X-half row kernel lives in the plan module");
-}
-
 // ---- ADMM: the two work spectra -> V and H V (padded, no shift) ------------------------------------------------
 int admm_rows_inv(Engine* e, real* Vout, real* HVout, bool skip_hv_outside) {
   if (e->mod && e->mod->admm_rows_inv) return e->mod->admm_rows_inv(e, Vout, HVout, skip_hv_outside ? 1 : 0);
@@ -80,7 +73,7 @@ int admm_rows_inv(Engine* e, real* Vout, real* HVout, bool skip_hv_outside) {
   real2* SA = e->S;
   real2* SB = e->S + (size_t)e->P * g.cplane;
   const Fft1dPlan& pinv = e->rows_r2 ? e->planWi : e->planW;
-  if (e->rows_half)
+  if (e->plan.rows_half)
     return dispatch_row(g.Wp / 2, e->planWh.skew_ok, false, [&](auto NTc, auto EM, auto SK, auto) {
       constexpr int nt = decltype(NTc)::value, em = decltype(EM)::value;
       constexpr bool sk = decltype(SK)::value;
