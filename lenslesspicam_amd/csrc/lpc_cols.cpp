@@ -18,26 +18,18 @@ int cols_passA(Engine* e, real2* S, int nplanes, bool inverse, int zr0, int zr1,
     cp.needn = g.H;
   }
   if (e->mod && e->mod->cols_passA) return e->mod->cols_passA(e, &cp, S, nplanes, inverse ? 1 : 0, kid);
-  const dim3 grid(cp.G * cp.ntile_c, nplanes);
   return dispatch_cfg(cp.N * cp.T, [&](auto NT, auto EM) {
-    constexpr int nt = decltype(NT)::value, em = decltype(EM)::value;
-    const size_t smem = (size_t)cp.N * cp.T * sizeof(real2);
-    if (inverse) return launch_k(e, kid, k_cols<nt, em, true>, grid, nt, smem, g, e->planA, cp, S);
-    return launch_k(e, kid, k_cols<nt, em, false>, grid, nt, smem, g, e->planA, cp, S);
+    return launch_cols<NT.value, EM.value, 0, false>(e, e->planA, cp, S, nplanes, inverse, kid);
   });
 }
 
 // plain forward pass B (setup transforms only)
 int cols_passB_fwd(Engine* e, real2* S, int nplanes, int zr0, int zr1) {
-  const PlaneGeom& g = e->g;
   ColPass cp = e->passB;
   cp.tw_mode = 0;
   cp.zr0 = zr0; cp.zr1 = zr1;
-  const dim3 grid(cp.G * cp.ntile_c, nplanes);
   return dispatch_cfg(cp.N * cp.T, [&](auto NT, auto EM) {
-    constexpr int nt = decltype(NT)::value, em = decltype(EM)::value;
-    return launch_k(e, -1, k_cols<nt, em, false>, grid, nt, (size_t)cp.N * cp.T * sizeof(real2), g, e->planB,
-                    cp, S);
+    return launch_cols<NT.value, EM.value, 0, false>(e, e->planB, cp, S, nplanes, false, -1);
   });
 }
 
@@ -51,14 +43,12 @@ int conv_middle(Engine* e, real2* S, int nplanes, bool adjoint, int zr0, int zr1
   cp.zr0 = split ? 0 : zr0;
   cp.zr1 = split ? g.Hp : zr1;
   const dim3 grid(cp.G * cp.ntile_c, nplanes);
-  const real hscale = (real)1.0 / ((real)g.Hp * (real)g.Wp);
+  const real hscale = inv_points(g);
   // LaunchPlan::conv_mid_reg: one lane = one whole pass-B column transform in registers
   auto reg_mid = [&](auto kernel) {
     const dim3 rgrid((g.Wc + 63) / 64, cp.G, nplanes);
-    PlaneGeom gl = g;
-    gl.rev = e->plan.gd_rev_mid ? 1 : 0;       // PlaneGeom::rev
-    return launch_k(e, LPC_K_COL_MID, kernel, rgrid, 64, 0, gl, e->planB, cp, S, (const real2*)e->Hs,
-                    adjoint ? 1 : 0, hscale, e->Ppsf);
+    return launch_k(e, LPC_K_COL_MID, kernel, rgrid, 64, 0, geom_rev(e, e->plan.gd_rev_mid), e->planB, cp, S,
+                    (const real2*)e->Hs, adjoint ? 1 : 0, hscale, e->Ppsf);
   };
   const int regN = e->plan.conv_mid_reg;
   if (regN == 48) { LPC_OK(reg_mid(k_cols_mid_mul_reg<8, 6>)); }
@@ -80,8 +70,6 @@ int conv_middle(Engine* e, real2* S, int nplanes, bool adjoint, int zr0, int zr1
 // ---- ADMM: [pass A] -> fused middle (V-hat, H V-hat) -> [inverse pass A] on the two work spectra ----------------
 int admm_cols(Engine* e, const AdmmScalars& sc) {
   const PlaneGeom& g = e->g;
-  real2* SA = e->S;
-  real2* SB = e->S + (size_t)e->P * g.cplane;
   const bool split = e->plan.N1 > 1;
   // sc.skipa: the rows of SB outside the sensor window were not re-transformed, they still hold what the last inverse
   // row pass consumed = rfft(HV row) / Wp; a = mu1 HV there
@@ -93,13 +81,11 @@ int admm_cols(Engine* e, const AdmmScalars& sc) {
     cp.gb = e->g_sep ? e->Gb : nullptr;
     cp.rev = e->plan.rev_mid ? 1 : 0;
     cp.swz = e->plan.mid_swz;
-    const dim3 grid(cp.G * cp.ntile_c, e->P);
-    const FastDiv t2 = make_fastdiv((unsigned)(2 * cp.T));
     const AdmmMid mid = e->plan.admm_mid;
     if (mid == ADMM_MID_REG24) {
       LPC_OK(launch_k(e, LPC_K_COL_MID, k_cols_mid_admm_reg<8, 3>, dim3((g.Wc + 63) / 64, cp.G, e->P), 64, 0, g, e->planB,
-                      cp, SA, SB, (const real2*)e->Hs, (const real*)e->Gabs, (const real2*)e->phr, (const real2*)e->phc,
-                      sc.mu1, sc.mu2, sc.mu3, (real)1.0 / ((real)g.Hp * (real)g.Wp)));
+                      cp, e->S, spec_b(e), (const real2*)e->Hs, (const real*)e->Gabs, (const real2*)e->phr,
+                      (const real2*)e->phc, sc.mu1, sc.mu2, sc.mu3, inv_points(g)));
     } else if (mid == ADMM_MID_MODULE) {   // compile-time plan in LDS: both spectra side by side, or one at a time
       if (e->midc && !(e->midc_valid && e->midc_par[0] == (double)sc.mu1 && e->midc_par[1] == (double)sc.mu2 &&
                        e->midc_par[2] == (double)sc.mu3)) {      // k_mid_consts: once per (PSF, step sizes)
@@ -107,7 +93,7 @@ int admm_cols(Engine* e, const AdmmScalars& sc) {
         auto consts = [&](auto kernel) {
           return launch_k(e, -1, kernel, grid1d(n, 256, e->Ppsf), 256, 0, (const real2*)e->Hs_t, (const real*)e->Gabs_t,
                           cp.ga, cp.gb, (const real2*)e->phr, (const real2*)e->phc, g.Hp, g.Wc, g.cpitch, g.cplane, sc.mu1,
-                          sc.mu2, sc.mu3, (real)1.0 / ((real)g.Hp * (real)g.Wp), e->midc, e->midrd);
+                          sc.mu2, sc.mu3, inv_points(g), e->midc, e->midrd);
         };
         if (e->plan.spec.mid_pc == 2) LPC_OK(consts(k_mid_consts<256, true>));
         else LPC_OK(consts(k_mid_consts<256, false>));
@@ -116,16 +102,10 @@ int admm_cols(Engine* e, const AdmmScalars& sc) {
       }
       LPC_OK(e->mod->admm_mid(e, &cp, &sc, (sc.skipa && !split) ? sc.mu1 * (real)g.Wp : (real)0.));
     } else if (mid == ADMM_MID_RT_512X18) {
-      LPC_OK(launch_k(e, LPC_K_COL_MID, k_cols_mid_admm<512, 18>, grid, 512, (size_t)cp.N * cp.T * 2 * sizeof(real2),
-                      g, e->planB, cp, SA, SB, (const real2*)e->Hs, (const real*)e->Gabs, (const real2*)e->phr,
-                      (const real2*)e->phc, t2, sc.mu1, sc.mu2, sc.mu3, (real)1.0 / ((real)g.Hp * (real)g.Wp), (real)0.));
+      LPC_OK((launch_admm_mid<512, 18, 0, false, 0>(e, e->planB, cp, sc, (real)0.)));
     } else
-    LPC_OK(dispatch_cfg(cp.N * cp.T * 2, [&](auto NTc, auto EM) {
-      constexpr int nt = decltype(NTc)::value, em = decltype(EM)::value;
-      return launch_k(e, LPC_K_COL_MID, k_cols_mid_admm<nt, em>, grid, nt,
-                      (size_t)cp.N * cp.T * 2 * sizeof(real2), g, e->planB, cp, SA, SB, (const real2*)e->Hs,
-                      (const real*)e->Gabs, (const real2*)e->phr, (const real2*)e->phc, t2, sc.mu1, sc.mu2,
-                      sc.mu3, (real)1.0 / ((real)g.Hp * (real)g.Wp), (real)0.);
+    LPC_OK(dispatch_cfg(cp.N * cp.T * 2, [&](auto NT, auto EM) {
+      return launch_admm_mid<NT.value, EM.value, 0, false, 0>(e, e->planB, cp, sc, (real)0.);
     }));
   }
   if (split) LPC_OK(cols_passA(e, e->S, 2 * e->P, true, 0, g.Hp, LPC_K_COL_A_INV));

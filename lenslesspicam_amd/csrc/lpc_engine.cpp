@@ -497,8 +497,9 @@ static void finish_plan(Engine* e, int cu) {
   // every kernel starts where its predecessor finished): 12 MP FISTA 75.4 / 74.1 / 73.8 -> 74.5 / 73.0 / 72.8 ms per 40 iterations
   // on three instances of one box against the middle alone (r03z_ab.log); no effect at 1080p, where nothing is reversed
   const int gd_rev = o.gd_rev >= 0 ? o.gd_rev : ((size_t)g.cplane * e->P * sizeof(real2) > ((size_t)200 << 20)) ? 7 : 0;
-  pl.gd_rev_resid = gd_rev & 1;
-  pl.gd_rev_update = gd_rev & 2;
+  const bool mod_gd_rows = e->mod && e->mod->gd_rows_mid;     // the run-time-plan row kernels walk forwards only
+  pl.gd_rev_resid = mod_gd_rows && (gd_rev & 1);
+  pl.gd_rev_update = mod_gd_rows && (gd_rev & 2);
   pl.gd_rev_mid = gd_rev & 4;
   // pairs of column tiles on one XCD: measured (profiles/r03_notes.md) -6 % on the 5-iteration C1 call, whose 8-column
   // tiles read half cache lines (middle 0.0278 -> 0.0228 ms); at 12 MP (16 columns = whole lines) it removes a third of

@@ -1,12 +1,15 @@
 // lpc_engine.h -- what the translation units of the engine share: the handle, error plumbing, the launcher and the
-// workgroup-shape dispatchers, and the host functions that cross translation units.
+// workgroup-shape dispatchers, the host functions that cross translation units, and the launches of the kernels that
+// the library and its plan modules both hold (lpc_launch.h; the gradient-descent family's: lpc_gd_launch.h).
 //
 // The library is split so that the device compiler works on several units in parallel:
 //   lpc_engine.cpp  plans, geometry, HBM workspace, the C ABI, the image-domain ADMM kernels, set-up / layout /
 //                   evaluation / preparation kernels
 //   lpc_rows.cpp    every row-pass launch (real <-> half-spectrum transforms, incl. the fused ADMM rows)
 //   lpc_cols.cpp    every column-pass launch (pass A, the fused middles)
-//   lpc_gd.cpp, lpc_gd_update.cpp, lpc_gd_update_fwd.cpp   the gradient-descent family's fused row kernels
+//   lpc_gd.cpp, lpc_gd_update.cpp, lpc_gd_update_p0.cpp, lpc_gd_update_p1.cpp   the gradient-descent family's fused row
+//                   kernels (the update rows in three units: half-length rows, paired rows without / with the folded
+//                   radix-2 stage)
 //   lpc_jit.cpp     plan modules: find / compile / load (lpc_plan.h)
 //   lpc_module.cpp  NOT part of the library: the source of a plan module (compile-time-plan kernels of one frame shape)
 #pragma once
@@ -304,6 +307,8 @@ int cols_passA(Engine* e, real2* S, int nplanes, bool inverse, int zr0, int zr1,
 int cols_passB_fwd(Engine* e, real2* S, int nplanes, int zr0, int zr1);
 int conv_middle(Engine* e, real2* S, int nplanes, bool adjoint, int zr0, int zr1, bool crop_rows_only = false);
 int admm_cols(Engine* e, const AdmmScalars& sc);   // sc.skipa: forward pass A rescales the kept rows of SB                // [pass A] -> fused ADMM middle -> [inverse pass A]
-// lpc_gd.cpp, lpc_gd_update.cpp, lpc_gd_update_fwd.cpp (one kernel family each)
+// lpc_gd.cpp, lpc_gd_update.cpp (one kernel family each)
 int gd_rows_mid(Engine* e);                                     // irfft rows -> residual -> rfft rows (S -> S2)
 int gd_rows_update(Engine* e, const GdScalars& sc, const real* alpha);   // irfft rows -> fused projected update
+
+#include "lpc_launch.h"

@@ -3,8 +3,7 @@
 // spread over three translation units that the device compiler works on in parallel: this one (one real row per
 // half-length transform) and lpc_gd_update_p0.cpp / lpc_gd_update_p1.cpp (paired rows without / with the folded radix-2
 // stage).
-#include "lpc_engine.h"
-#include "lpc_gd_kernels.h"
+#include "lpc_gd_launch.h"
 
 int gd_rows_update_paired_r2(Engine* e, const GdScalars& sc, const real* alpha);   // lpc_gd_update_p1.cpp
 int gd_rows_update_paired_plain(Engine* e, const GdScalars& sc, const real* alpha);   // lpc_gd_update_p0.cpp
@@ -14,12 +13,8 @@ int gd_rows_update(Engine* e, const GdScalars& sc, const real* alpha) {
   const PlaneGeom& g = e->g;
   if (e->mod && e->mod->gd_rows_update) return e->mod->gd_rows_update(e, &sc, alpha);
   if (e->plan.rows_half)
-    return dispatch_row(g.Wp / 2, e->planWh.skew_ok, false, [&](auto NTc, auto EM, auto SK, auto) {
-      constexpr int nt = decltype(NTc)::value, em = decltype(EM)::value;
-      constexpr bool sk = decltype(SK)::value;
-      return launch_k(e, LPC_K_SPATIAL, k_rinv_gd_update_half<nt, em, sk>, dim3(g.H, e->P), nt,
-                      LPC_ROW_SMEM_BYTES(g.Wp / 2, sk), g, e->planWh, e->planW.tw, (const real2*)e->S2, e->gx,
-                      e->gaux, alpha, sc);
+    return dispatch_row(g.Wp / 2, e->planWh.skew_ok, false, [&](auto NT, auto EM, auto SK, auto) {
+      return launch_gd_rows_update_half<NT.value, EM.value, SK.value>(e, e->planWh, sc, alpha);
     });
   return e->rows_r2 ? gd_rows_update_paired_r2(e, sc, alpha) : gd_rows_update_paired_plain(e, sc, alpha);
 }

@@ -2,10 +2,10 @@
 // frame shape, plus their launchers.  Compiled on its own into <libdir>/modules/lpcmod_<key>.so with the -D flags of
 // plan_spec_defines() (lpc_plan.h): by build.py for BASELINE.json's shapes, by lpc_create() itself (lpc_jit.cpp) for any
 // other shape on first use.  The core library loads it with dlopen and calls the launchers through the LpcModule table;
-// a launcher is the static branch of the core's own launch code (lpc_rows.cpp / lpc_cols.cpp / lpc_gd.cpp) with every
-// plan choice turned into a constant.  Nothing here is shape-specific source: the shape arrives as macros.
-#include "lpc_engine.h"
-#include "lpc_gd_kernels.h"
+// a launcher here is the core's own launcher (lpc_launch.h, lpc_gd_launch.h) with every plan choice turned into a
+// constant, or the one launch of a kernel that only modules hold.  Nothing here is shape-specific source: the shape
+// arrives as macros.
+#include "lpc_gd_launch.h"
 #include "lpc_gd_v2_kernels.h"
 
 #ifndef LPC_MOD_MID_PRE
@@ -20,12 +20,6 @@
 #ifndef LPC_MOD_FAMILY
 #error "lpc_module.cpp is compiled with the flags of plan_spec_defines() (lpc_plan.h)"
 #endif
-
-static inline PlaneGeom geom_rev(const Engine* e, bool rev) {   // the launch's copy of the geometry (PlaneGeom::rev)
-  PlaneGeom g = e->g;
-  g.rev = rev ? 1 : 0;
-  return g;
-}
 
 // ============================================================================== rows ==
 #if LPC_MOD_ROW_KIND != 0
@@ -44,40 +38,23 @@ static const size_t kRowSmem = LPC_ROW_SMEM_BYTES(RowP::n, RSK);
 static RowPA row_arg(const Engine* e) { return splan_arg<RowP, LPC_MOD_TW_LANE != 0>(e->planWh, e->tws_row); }
 
 static int m_rows_fwd_single(Engine* e, const RealSrc* src, real2* S, int nplanes, int kid) {
-  return launch_k(e, kid, k_rfwd_rows_half<RNT, REM, RSK, RowPA>, dim3(src->nrows, nplanes), RNT, kRowSmem, e->g,
-                  row_arg(e), e->planW.tw, *src, S);
+  return launch_rows_fwd_half<RNT, REM, RSK>(e, row_arg(e), *src, S, nplanes, kid);
 }
 static int m_rows_inv_single(Engine* e, const real2* S, const RealDst* dst, int nplanes, int kid) {
-  return launch_k(e, kid, k_rinv_rows_half<RNT, REM, RSK, RowPA>, dim3(dst->nrows, nplanes), RNT, kRowSmem, e->g,
-                  row_arg(e), e->planW.tw, S, *dst);
+  return launch_rows_inv_half<RNT, REM, RSK>(e, row_arg(e), S, *dst, nplanes, kid);
 }
 #if LPC_MOD_FAMILY == LPC_FAM_ADMM
-static int m_admm_rows_fwd(Engine* e) {
-  const PlaneGeom& g = e->g;
-  real2* SA = e->S;
-  real2* SB = e->S + (size_t)e->P * g.cplane;
-  return launch_k(e, LPC_K_ROW_FWD, k_rfwd_half<RNT, REM, RSK, RowPA>, dim3(2 * g.Hp, e->P), RNT, kRowSmem, g,
-                  row_arg(e), e->planW.tw, (const real*)e->Rsp, (const real*)e->Aarr, SA, SB);
-}
+static int m_admm_rows_fwd(Engine* e) { return launch_admm_rows_fwd_half<RNT, REM, RSK>(e, row_arg(e)); }
 static int m_admm_rows_inv(Engine* e, real* Vout, real* HVout, int skip_hv_outside) {
-  const PlaneGeom& g = e->g;
-  real2* SA = e->S;
-  real2* SB = e->S + (size_t)e->P * g.cplane;
-  const int hrows = skip_hv_outside ? g.Hp + g.H : 2 * g.Hp;
-  return launch_k(e, LPC_K_ROW_INV, k_rinv_half<RNT, REM, RSK, RowPA>, dim3(hrows, e->P), RNT, kRowSmem,
-                  e->g, row_arg(e),
-                  e->planW.tw, (const real2*)SA, (const real2*)SB, Vout, HVout, skip_hv_outside ? 1 : 0);
+  return launch_admm_rows_inv_half<RNT, REM, RSK>(e, row_arg(e), Vout, HVout, skip_hv_outside != 0);
 }
 #if LPC_MOD_ROW_X
 static int m_admm_rows_fwd_x(Engine* e, const AdmmScalars* sc, const K1Rows* k1) {
   if (k1) return fail("internal: half-length rows do not hold the TV / W half");
-  const PlaneGeom& g = e->g;
-  real2* SA = e->S;
-  real2* SB = e->S + (size_t)e->P * g.cplane;
-  return launch_k(e, LPC_K_ROW_FWD, k_rfwd_half_x<RNT, REM, RSK, RowPA>, dim3(2 * g.Hp, e->P), RNT, kRowSmem,
+  return launch_k(e, LPC_K_ROW_FWD, k_rfwd_half_x<RNT, REM, RSK, RowPA>, dim3(2 * e->g.Hp, e->P), RNT, kRowSmem,
                   e->g, *sc,
                   row_arg(e), (const real2*)e->planW.tw, (const real*)e->Rsp, (const real*)e->HVb[e->hcur],
-                  (const real*)e->HVb[e->hcur ^ 1], e->xi, (const real*)e->Y, SA, SB);
+                  (const real*)e->HVb[e->hcur ^ 1], e->xi, (const real*)e->Y, e->S, spec_b(e));
 }
 #endif
 #else   // gradient-descent family
@@ -99,15 +76,10 @@ static int m_gd_rows_mid(Engine* e) {
                       (const real*)e->Y, make_fastdiv((unsigned)g.DC), make_fastdiv((unsigned)g.C));
   }
 #endif
-  return launch_k(e, LPC_K_ROW_INV, k_rinv_gd_mid_half<RNT, REM, RSK, RowPA>, dim3(g.H, e->P), RNT, kRowSmem,
-                  geom_rev(e, e->plan.gd_rev_resid),
-                  row_arg(e), e->planW.tw, (const real2*)e->S, e->S2, (const real*)e->Y);
+  return launch_gd_rows_mid_half<RNT, REM, RSK>(e, row_arg(e));
 }
 static int m_gd_rows_update(Engine* e, const GdScalars* sc, const real* alpha) {
-  const PlaneGeom& g = e->g;
-  return launch_k(e, LPC_K_SPATIAL, k_rinv_gd_update_half<RNT, REM, RSK, RowPA>, dim3(g.H, e->P), RNT, kRowSmem,
-                  geom_rev(e, e->plan.gd_rev_update),
-                  row_arg(e), e->planW.tw, (const real2*)e->S2, e->gx, e->gaux, alpha, *sc);
+  return launch_gd_rows_update_half<RNT, REM, RSK>(e, row_arg(e), *sc, alpha);
 }
 static int m_gd_rows_update_fwd(Engine* e, const GdScalars* sc, const real* alpha) {
   const PlaneGeom& g = e->g;
@@ -137,31 +109,19 @@ static int m_gd_rows_update_fwd(Engine* e, const GdScalars* sc, const real* alph
 static RowPA row_arg(const Engine* e) { return splan_arg<RowP, LPC_MOD_TW_LANE != 0>(e->planW, e->tws_row); }
 
 static int m_admm_rows_fwd(Engine* e) {
-  const PlaneGeom& g = e->g;
-  real2* SA = e->S;
-  real2* SB = e->S + (size_t)e->P * g.cplane;
-  return launch_k(e, LPC_K_ROW_FWD, k_rfwd_arrays<RNT, REM, RSK, false, RowPA, LPC_MOD_SLAY>, dim3(paired_rows_grid(g, false), e->P), RNT, kRowSmem, g,
-                  row_arg(e), (const real*)e->Rsp, (const real*)e->Aarr, SA, SB);
+  return launch_admm_rows_fwd_paired<RNT, REM, RSK, false, LPC_MOD_SLAY>(e, row_arg(e));
 }
 static int m_admm_rows_inv(Engine* e, real* Vout, real* HVout, int skip_hv_outside) {
-  const PlaneGeom& g = e->g;
-  real2* SA = e->S;
-  real2* SB = e->S + (size_t)e->P * g.cplane;
-  const int irows = paired_rows_grid(g, skip_hv_outside != 0);
-  return launch_k(e, LPC_K_ROW_INV, k_rinv_arrays<RNT, REM, RSK, false, RowPA, LPC_MOD_SLAY>, dim3(irows, e->P), RNT, kRowSmem,
-                  e->g,
-                  row_arg(e), (const real2*)SA, (const real2*)SB, Vout, HVout, skip_hv_outside ? 1 : 0);
+  return launch_admm_rows_inv_paired<RNT, REM, RSK, false, LPC_MOD_SLAY>(e, row_arg(e), Vout, HVout, skip_hv_outside != 0);
 }
 #if LPC_MOD_ROW_X
 // quads per lane and row with which the TV / W half can ride along: 1 or 2 (padded widths up to 8 x the lanes), else 0
 constexpr int kK1Quads = (RowP::n >> 2) <= RNT ? 1 : ((RowP::n >> 2) <= 2 * RNT ? 2 : 0);
 constexpr bool kK1Rows = kK1Quads != 0;
 static int m_admm_rows_fwd_x(Engine* e, const AdmmScalars* sc, const K1Rows* k1) {
-  const PlaneGeom& g = e->g;
-  real2* SA = e->S;
-  real2* SB = e->S + (size_t)e->P * g.cplane;
+  real2 *SA = e->S, *SB = spec_b(e);
   // sc->skipa: `a` on the rows of the sensor window alone
-  const int xrows = paired_rows_grid(g, sc->skipa != 0);
+  const int xrows = paired_rows_grid(e->g, sc->skipa != 0);
   if (k1) {
     if constexpr (kK1Rows)
       return launch_k(e, LPC_K_ROW_FWD, k_rfwd_arrays_x<RNT, REM, RSK, RowPA, true, LPC_MOD_SLAY>, dim3(xrows, e->P), RNT, kRowSmem,
@@ -181,15 +141,10 @@ static int m_admm_rows_fwd_x(Engine* e, const AdmmScalars* sc, const K1Rows* k1)
 // ============================================================================ pass A ==
 #if LPC_MOD_PASSA
 typedef SPlan<LPC_MOD_PASSA_RAD> PassAP;
-typedef SPlanArg<PassAP> PassAPA;
 // cp: the engine's pass-A descriptor with this call's mode, zero rows and scale already set (cols_passA)
 static int m_cols_passA(Engine* e, const ColPass* cp, real2* S, int nplanes, int inverse, int kid) {
-  constexpr int NT = LPC_MOD_PASSA_NT, EM = LPC_MOD_PASSA_EM, T = LPC_MOD_PASSA_T;
-  const dim3 grid(cp->G * cp->ntile_c, nplanes);
-  const size_t smem = (size_t)PassAP::n * (T + 2) * sizeof(real2);   // tile + the plan's and the four-step twiddles
-  const PassAPA pa = splan_arg<PassAP>(e->planA);
-  if (inverse) return launch_k(e, kid, k_cols<NT, EM, true, PassAPA, T, true>, grid, NT, smem, e->g, pa, *cp, S);
-  return launch_k(e, kid, k_cols<NT, EM, false, PassAPA, T, true>, grid, NT, smem, e->g, pa, *cp, S);
+  return launch_cols<LPC_MOD_PASSA_NT, LPC_MOD_PASSA_EM, LPC_MOD_PASSA_T, true>(e, splan_arg<PassAP>(e->planA), *cp, S,
+                                                                                nplanes, inverse != 0, kid);
 }
 #endif
 
@@ -199,25 +154,17 @@ typedef SPlan<LPC_MOD_MID_RAD> MidP;
 typedef SPlanArg<MidP> MidPA;
 static int m_admm_mid(Engine* e, const ColPass* cp, const AdmmScalars* sc, real sb_outside_scale) {
   constexpr int NT = LPC_MOD_MID_NT, EM = LPC_MOD_MID_EM, T = LPC_MOD_MID_T;
-  const PlaneGeom& g = e->g;
-  real2* SA = e->S;
-  real2* SB = e->S + (size_t)e->P * g.cplane;
   const MidPA pa = splan_arg<MidP>(e->planB);
-  const real rscale = (real)1.0 / ((real)g.Hp * (real)g.Wp);
 #if LPC_MOD_MID_KIND == LPC_MID_SEQ     // single-pass columns, one spectrum at a time through T columns
   // (LDS: the tile + the plan's twiddle table behind it)
   constexpr int PC = LPC_MOD_SLAY != 0 ? LPC_MOD_MID_PC : 0;      // precombined point-wise constants (k_mid_consts)
   return launch_k(e, LPC_K_COL_MID, k_cols_mid_admm_seq<NT, EM, MidPA, T, LPC_MOD_MID_MINW, LPC_MOD_MID_PRE != 0, LPC_MOD_SLAY, PC>,
-                  dim3(cp->ntile_c * e->P), NT, (size_t)MidP::n * (T + 1) * sizeof(real2), g, pa, *cp, SA, SB,
+                  dim3(cp->ntile_c * e->P), NT, (size_t)MidP::n * (T + 1) * sizeof(real2), e->g, pa, *cp, e->S, spec_b(e),
                   PC ? (const real2*)e->midc : (const real2*)(LPC_MOD_SLAY ? e->Hs_t : e->Hs),
                   PC ? (const real*)e->midrd : (const real*)(LPC_MOD_SLAY ? e->Gabs_t : e->Gabs), (const real2*)e->phr, (const real2*)e->phc, sc->mu1,
-                  sc->mu2, sc->mu3, rscale, sb_outside_scale);
+                  sc->mu2, sc->mu3, inv_points(e->g), sb_outside_scale);
 #else                                   // both spectra side by side: [N][2 T]
-  const FastDiv t2 = make_fastdiv((unsigned)(2 * T));
-  return launch_k(e, LPC_K_COL_MID, k_cols_mid_admm<NT, EM, MidPA, 2 * T, true, LPC_MOD_SLAY>, dim3(cp->G * cp->ntile_c, e->P), NT,
-                  (size_t)MidP::n * (2 * T + 1) * sizeof(real2), g, pa, *cp, SA, SB, (const real2*)(LPC_MOD_SLAY ? e->Hs_t : e->Hs),
-                  (const real*)(LPC_MOD_SLAY ? e->Gabs_t : e->Gabs), (const real2*)e->phr, (const real2*)e->phc, t2, sc->mu1, sc->mu2, sc->mu3,
-                  rscale, sb_outside_scale);
+  return launch_admm_mid<NT, EM, 2 * T, true, LPC_MOD_SLAY>(e, pa, *cp, *sc, sb_outside_scale);
 #endif
 }
 #endif
