@@ -185,6 +185,29 @@ int lpc_set_admm_schedule(lpc_handle h, int n, const double* mu1, const double* 
  * HOST arrays of n*C and n floats.  n <= 0 returns to the plain FISTA recursion. */
 int lpc_set_fista_schedule(lpc_handle h, int n, const lpc_real* alpha, const lpc_real* coef, void* stream);
 
+/* Reverse mode of the unrolled FISTA iterations (unrolled_fista.py:102-106 differentiated; what torch.autograd does
+ * in the reference's training loop).  FISTA handles with a schedule (lpc_set_fista_schedule) only.
+ * lpc_fista_record(h, 1): from the next lpc_reset on, lpc_iterate keeps the tape -- the iterate and x_k of every
+ * iteration, (2 n + 1) un-padded state arrays, plus three work arrays and the partial sums of the reductions
+ * (n * B * D * C * H * 2 doubles), allocated for the schedule's n iterations and counted in lpc_workspace_bytes; the
+ * recorded forward launches the same kernels as the unrecorded one.  lpc_fista_record(h, 0) frees it (this waits for the
+ * stream); lpc_fista_record(h, -1) pauses: nothing is recorded from the next lpc_reset on, the tape stays allocated (no
+ * wait, no allocation: what a training loop that alternates with evaluation wants).  lpc_set_fista_schedule and
+ * lpc_set_data invalidate what was recorded.
+ * lpc_fista_backward: given dL/d(lpc_form_image) it writes the gradients w.r.t. the measurement, the schedule's alpha[]
+ * and coef[] and the initial estimate.  Asynchronous on `stream`, device memory only, no synchronisation; the tape and
+ * the solver state stay intact (it may be called again: the same bits come out).  It fails, with a message, when: the
+ * handle is not a FISTA handle / has no schedule / does not record; the iterations since the reset are not exactly the
+ * schedule's; the padded height or width is odd (the recursion uses convolve and deconvolve as each other's adjoints,
+ * which they are for even padded lengths only); depth > 1; a split iteration is pending; an alpha of the schedule is 0. */
+int lpc_fista_record(lpc_handle h, int on);
+int lpc_fista_backward(lpc_handle h, const lpc_real* dev_grad_out,   /* (B,D,H,W,C): dL/d(lpc_form_image)        */
+                       lpc_real* dev_grad_data,    /* (B,H,W,data_channels) or NULL                            */
+                       lpc_real* dev_grad_alpha,   /* n*C, gradient w.r.t. the alpha[] given to the schedule   */
+                       lpc_real* dev_grad_coef,    /* n,   gradient w.r.t. coef[]                               */
+                       lpc_real* dev_grad_init,    /* (B,D,H,W,C) or NULL: w.r.t. the initial estimate          */
+                       void* stream);
+
 /* ---- the hot loop: `for i in range(n_iter): self._update(i)`  recon.py:575-576 ------ */
 /* exactly n_iter iterations, asynchronous on `stream`; no early exit exists on this path */
 int lpc_iterate(lpc_handle h, int n_iter, void* stream);

@@ -127,6 +127,8 @@ class Lib:
             "lpc_set_admm_schedule": [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double), C.POINTER(C.c_double)],
             "lpc_set_fista_schedule": [vp, C.c_int, vp, vp, vp],
+            "lpc_fista_record": [vp, C.c_int],
+            "lpc_fista_backward": [vp, fp, fp, fp, fp, fp, vp],
             "lpc_form_image": [vp, fp, vp],
             "lpc_get_state": [vp, C.c_char_p, fp, vp],
             "lpc_profile_enable": [vp, C.c_int],
@@ -265,6 +267,16 @@ class Handle:
         a = (self.lib.c_real * len(flat))(*flat)
         c = (self.lib.c_real * n)(*[float(v) for v in coef])
         self._c(self.lib.dll.lpc_set_fista_schedule(self.h, n, C.cast(a, C.c_void_p), C.cast(c, C.c_void_p), stream))
+
+    def fista_record(self, on=True):
+        """the tape of the unrolled FISTA iterations from the next ``reset`` on (lpc_fista_record): True / 1 keep it,
+        False / 0 free it, -1 stop recording but keep the memory"""
+        self._c(self.lib.dll.lpc_fista_record(self.h, int(on)))
+
+    def fista_backward(self, grad_out_ptr, grad_data_ptr, grad_alpha_ptr, grad_coef_ptr, grad_init_ptr=None, stream=0):
+        """reverse sweep over the tape: device pointers; ``grad_data_ptr`` / ``grad_init_ptr`` may be None"""
+        self._c(self.lib.dll.lpc_fista_backward(self.h, grad_out_ptr, grad_data_ptr, grad_alpha_ptr, grad_coef_ptr,
+                                                grad_init_ptr, stream))
 
     def clear_admm_schedule(self):
         self._c(self.lib.dll.lpc_set_admm_schedule(self.h, 0, None, None, None, None))

@@ -6,6 +6,7 @@
 #include <mutex>
 #include <unordered_map>
 #include "lpc_gd_kernels.h"
+#include "lpc_gd_bwd_kernels.h"
 #include "lpc_metric_kernels.h"
 #include "lpc_prep_kernels.h"
 
@@ -1057,6 +1058,8 @@ int lpc_set_data(lpc_handle e, const real* dev_data, int data_channels, void* st
   const PlaneGeom& g = e->g;
   LPC_OK(hwc_to_planar(e, dev_data, e->Y, e->cfg.batch, g.H, g.W, g.W, g.uplane, data_channels));
   e->data_set = true;
+  e->data_channels = data_channels;
+  e->tape_iters = -1;      // a tape recorded with other data no longer matches (lpc_fista_backward refuses)
   return 0;
 }
 
@@ -1113,6 +1116,7 @@ int lpc_set_fista_schedule(lpc_handle e, int n, const real* alpha, const real* c
   e->stream = (lpcStream_t)stream;
   e->fista_coef.clear();
   e->fista_sched_n = 0;
+  e->tape_iters = -1;      // a tape recorded with another schedule no longer matches (lpc_fista_backward refuses)
   if (n <= 0) return 0;
   if (!alpha || !coef) return fail("lpc_set_fista_schedule: null array");
   const int C = e->cfg.channels;
@@ -1129,8 +1133,41 @@ int lpc_set_fista_schedule(lpc_handle e, int n, const real* alpha, const real* c
   }
   LPC_OK(upload(e, e->galpha_sched, alpha, (size_t)n * C * sizeof(real)));
   e->fista_coef.assign(coef, coef + n);
+  e->fista_alpha.assign(alpha, alpha + (size_t)n * C);
   e->fista_sched_n = n;
   return 0;
+}
+
+int lpc_fista_record(lpc_handle e, int on) {
+  if (!e) return fail("null handle");
+  if (e->cfg.algo != LPC_ALGO_FISTA) return fail("lpc_fista_record: not a FISTA handle");
+  e->rec_on = on > 0;
+  e->tape_iters = -1;
+  if (on < 0) return 0;                                    // pause: the tape stays allocated, nothing is recorded
+  if (!e->rec_on) { gd_tape_free(e); return 0; }
+  return e->fista_sched_n > 0 ? gd_tape_alloc(e) : 0;     // (no schedule yet: lpc_reset allocates)
+}
+
+int lpc_fista_backward(lpc_handle e, const real* dev_grad_out, real* dev_grad_data, real* dev_grad_alpha,
+                       real* dev_grad_coef, real* dev_grad_init, void* stream) {
+  if (!e || !dev_grad_out || !dev_grad_alpha || !dev_grad_coef) return fail("lpc_fista_backward: null argument");
+  if (e->cfg.algo != LPC_ALGO_FISTA) return fail("lpc_fista_backward: not a FISTA handle");
+  if (e->fista_sched_n <= 0) return fail("lpc_fista_backward: the handle has no schedule (lpc_set_fista_schedule)");
+  if (!e->rec_on || !e->tape || e->tape_iters < 0)
+    return fail("lpc_fista_backward: nothing recorded (lpc_fista_record(h, 1), then lpc_reset and lpc_iterate)");
+  if (e->split_pending) return fail("lpc_fista_backward: a split iteration is in flight (lpc_iterate_end missing)");
+  if (e->iters_done != e->fista_sched_n || e->tape_iters != e->fista_sched_n || e->tape_n != e->fista_sched_n)
+    return fail("lpc_fista_backward: " + std::to_string(e->iters_done) + " iterations since the reset, the schedule has " +
+                std::to_string(e->fista_sched_n));
+  if ((e->g.Hp | e->g.Wp) & 1)
+    return fail("lpc_fista_backward: padded frame " + std::to_string(e->g.Hp) + " x " + std::to_string(e->g.Wp) +
+                " has an odd length: convolve and deconvolve are not each other's adjoints there (not implemented)");
+  if (e->cfg.depth > 1) return fail("lpc_fista_backward: depth > 1 is not implemented");
+  for (real a : e->fista_alpha)
+    if (a == (real)0.) return fail("lpc_fista_backward: a step alpha of the schedule is 0");
+  if (dev_grad_data && !e->data_set) return fail("lpc_fista_backward: no data set");
+  e->stream = (lpcStream_t)stream;
+  return gd_backward(e, dev_grad_out, dev_grad_data, dev_grad_alpha, dev_grad_coef, dev_grad_init);
 }
 
 int lpc_iterate(lpc_handle e, int n_iter, void* stream) {
@@ -1622,6 +1659,9 @@ int lpc_plan_info(lpc_handle e, char* buf, size_t n) {
                                       : " (xi inside the sensor window only)";
   }
   if (e->cfg.algo == LPC_ALGO_ADMM && e->g_sep) s += "; gram as row + column terms";
+  if (e->cfg.algo == LPC_ALGO_FISTA)      // lpc_fista_backward (lpc_gd_bwd.cpp: gd_bwd_rows)
+    s += e->mod && e->mod->gd_bwd_head ? "; reverse rows: plan module" : pl.rows_half ? "; reverse rows: half-length, run-time plan"
+                                                                                     : "; reverse rows: paired, run-time plan";
   s += e->mod ? "; plan module " + plan_spec_key(sp) : "; run-time plans (" + e->mod_note + ")";
   std::snprintf(buf, n, "%s", s.c_str());
   return 0;

@@ -10,6 +10,7 @@
 //   lpc_gd.cpp, lpc_gd_update.cpp, lpc_gd_update_p0.cpp, lpc_gd_update_p1.cpp   the gradient-descent family's fused row
 //                   kernels (the update rows in three units: half-length rows, paired rows without / with the folded
 //                   radix-2 stage)
+//   lpc_gd_bwd.cpp  reverse mode of unrolled FISTA: the fused row kernels of lpc_fista_backward
 //   lpc_jit.cpp     plan modules: find / compile / load (lpc_plan.h)
 //   lpc_module.cpp  NOT part of the library: the source of a plan module (compile-time-plan kernels of one frame shape)
 #pragma once
@@ -175,6 +176,16 @@ struct lpc_engine {
   real* galpha_sched = nullptr;  // device [n][C]
   size_t galpha_sched_cap = 0;   // elements allocated for it (re-used by later schedules that fit)
   int fista_sched_n = 0;
+  std::vector<real> fista_alpha;   // host copy of the schedule's alpha (lpc_fista_backward refuses a zero step)
+  // reverse mode (lpc_fista_record / lpc_fista_backward): the tape is ONE allocation of (2 n + 4) un-padded state arrays
+  //   y_0 .. y_n | xk_0 .. xk_{n-1} | work: gy / gz, carry, g_b      (y_i = gx before iteration i, xk_i = gaux after it)
+  // and the per-row partial sums of g_coef / g_alpha: n * P * H * 2 doubles
+  bool rec_on = false;
+  real* tape = nullptr;
+  double* tape_part = nullptr;
+  int tape_n = 0;              // iterations the tape was allocated for
+  long tape_iters = -1;        // iterations recorded since the last reset (-1: nothing recorded)
+  int data_channels = 0;       // of the last lpc_set_data
   // common
   real* Y = nullptr;         // data planes, un-padded [Pdata][H][W]
   real* init_est = nullptr;  // planar copy of the initial estimate (or null)
@@ -274,6 +285,7 @@ static inline RealDst dst_cropped(const Engine* e, real* base) {
 // ---- plan module: launchers of the compile-time-plan kernels of one frame shape (lpc_module.cpp) -------------------
 // An entry is null when the module does not hold that kernel; the core then launches its run-time-plan kernel.
 struct GdScalars;
+struct GdBwd;
 struct LpcModule {
   int (*rows_fwd_single)(Engine*, const RealSrc*, real2* S, int nplanes, int kid);
   int (*rows_inv_single)(Engine*, const real2* S, const RealDst*, int nplanes, int kid);
@@ -283,6 +295,9 @@ struct LpcModule {
   int (*gd_rows_mid)(Engine*);
   int (*gd_rows_update)(Engine*, const GdScalars*, const real* alpha);
   int (*gd_rows_update_fwd)(Engine*, const GdScalars*, const real* alpha);
+  int (*gd_bwd_head)(Engine*, const GdBwd*);       // reverse mode of unrolled FISTA (lpc_gd_bwd_kernels.h), half rows
+  int (*gd_bwd_mid)(Engine*, const GdBwd*);
+  int (*gd_bwd_update)(Engine*, const GdBwd*);
   int (*cols_passA)(Engine*, const ColPass*, real2* S, int nplanes, int inverse, int kid);
   int (*admm_mid)(Engine*, const ColPass*, const AdmmScalars*, real sb_outside_scale);
   int k1_rows;    // admm_rows_fwd_x takes the TV / W half of the image-domain work as well (k_rfwd_arrays_x<.., K1>)
@@ -310,5 +325,7 @@ int admm_cols(Engine* e, const AdmmScalars& sc);   // sc.skipa: forward pass A r
 // lpc_gd.cpp, lpc_gd_update.cpp (one kernel family each)
 int gd_rows_mid(Engine* e);                                     // irfft rows -> residual -> rfft rows (S -> S2)
 int gd_rows_update(Engine* e, const GdScalars& sc, const real* alpha);   // irfft rows -> fused projected update
+// lpc_gd_bwd.cpp
+int gd_bwd_rows(Engine* e, int mode, const GdBwd& a);           // reverse-mode rows: 0 head, 1 middle, 2 update + next head
 
 #include "lpc_launch.h"

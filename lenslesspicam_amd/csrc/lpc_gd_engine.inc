@@ -35,6 +35,39 @@ static int gd_apply_momentum_reset(Engine* e) {
   return 0;
 }
 
+// ---- the tape of the reverse mode (Engine::tape) ----
+static void gd_tape_free(Engine* e) {
+  if (!e->tape) return;
+  (void)rt::stream_sync(e->stream);
+  const size_t up = (size_t)e->g.uplane * e->P;
+  for (void* p : {(void*)e->tape, (void*)e->tape_part}) {
+    e->allocs.erase(std::remove(e->allocs.begin(), e->allocs.end(), p), e->allocs.end());
+    (void)rt::dev_free(p);
+  }
+  e->total_bytes -= (size_t)(2 * e->tape_n + 4) * up * sizeof(real) + (size_t)e->tape_n * e->P * e->g.H * 2 * sizeof(double);
+  e->tape = nullptr; e->tape_part = nullptr; e->tape_n = 0; e->tape_iters = -1;
+}
+static int gd_tape_alloc(Engine* e) {
+  const int n = e->fista_sched_n;
+  if (e->tape && e->tape_n == n) return 0;
+  gd_tape_free(e);
+  const size_t up = (size_t)e->g.uplane * e->P;
+  real* tape = nullptr;
+  double* part = nullptr;
+  LPC_OK(dev_alloc(e, &tape, (size_t)(2 * n + 4) * up));
+  if (dev_alloc(e, &part, (size_t)n * e->P * e->g.H * 2)) {      // all or nothing
+    e->allocs.pop_back();
+    e->total_bytes -= (size_t)(2 * n + 4) * up * sizeof(real);
+    (void)rt::dev_free(tape);
+    return 1;
+  }
+  e->tape = tape; e->tape_part = part; e->tape_n = n;
+  return 0;
+}
+static inline real* tape_y(Engine* e, int i) { return e->tape + (size_t)i * e->g.uplane * e->P; }
+static inline real* tape_xk(Engine* e, int i) { return e->tape + (size_t)(e->tape_n + 1 + i) * e->g.uplane * e->P; }
+static inline real* tape_work(Engine* e, int k) { return e->tape + (size_t)(2 * e->tape_n + 1 + k) * e->g.uplane * e->P; }
+
 static int gd_reset(Engine* e) {
   const PlaneGeom& g = e->g;
   const size_t ub = (size_t)g.uplane * e->P * sizeof(real);
@@ -57,6 +90,12 @@ static int gd_reset(Engine* e) {
   e->split_pending = false;
   e->gd_fwd_done = false;
   e->iters_done = 0;
+  e->tape_iters = -1;
+  if (e->rec_on && e->fista_sched_n > 0) {     // y_0 (= xk_{-1})
+    LPC_OK(gd_tape_alloc(e));
+    LPC_RT(rt::copy_d2d_async(tape_y(e, 0), e->gx, ub, e->stream));
+    e->tape_iters = 0;
+  }
   return 0;
 }
 
@@ -97,8 +136,55 @@ static int gd_iterate(Engine* e, int n_iter, int split = 0) {
     if (split) { e->split_pending = true; return 0; }
     if (e->cfg.algo == LPC_ALGO_FISTA) e->tk = tk_new;
     e->first = false;
+    if (e->tape_iters >= 0 && e->tape_iters == e->iters_done && e->iters_done < e->tape_n) {
+      // the tape: what the update just wrote, stream-ordered copies (the kernels are the unrecorded forward's)
+      const size_t ub = (size_t)g.uplane * e->P * sizeof(real);
+      LPC_RT(rt::copy_d2d_async(tape_xk(e, (int)e->iters_done), e->gaux, ub, e->stream));
+      LPC_RT(rt::copy_d2d_async(tape_y(e, (int)e->iters_done + 1), e->gx, ub, e->stream));
+      ++e->tape_iters;
+    }
     ++e->iters_done;
   }
+  return 0;
+}
+
+// reverse sweep over the tape (lpc_fista_backward; lpc_gd_bwd_kernels.h): per iteration the forward's five launches
+static int gd_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_alpha, real* grad_coef,
+                       real* grad_init) {
+  const PlaneGeom& g = e->g;
+  const int n = e->tape_n, C = e->cfg.channels;
+  const int rows = e->mod && e->mod->gd_bwd_head ? g.H : (e->plan.rows_half ? g.H : (g.H + 1) / 2);   // workgroups per plane
+  const long pstride = (long)e->P * rows * 2;
+  GdBwd a;
+  a.alpha = nullptr;
+  a.gz = tape_work(e, 0); a.carry = tape_work(e, 1); a.gb = grad_data ? tape_work(e, 2) : nullptr;
+  a.yn = tape_y(e, n);
+  a.gb_first = 0; a.tail = 0;
+  auto head_of = [&](int j) {
+    a.xk = tape_xk(e, j); a.xkp = j > 0 ? tape_xk(e, j - 1) : tape_y(e, 0); a.y = tape_y(e, j);
+    a.coef = e->fista_coef[(size_t)j];
+    a.part = e->tape_part + (long)j * pstride;
+  };
+  LPC_OK(hwc_to_planar(e, grad_out, a.gz, e->cfg.batch, g.H, g.W, g.W, g.uplane));
+  head_of(n - 1);
+  LPC_OK(gd_bwd_rows(e, 0, a));
+  for (int i = n - 1; i >= 0; --i) {
+    a.alpha = e->galpha_sched + (long)i * C;
+    LPC_OK(conv_middle(e, e->S, e->P, false, g.sh, g.sh + g.H, true));       // Cv(gz)
+    a.gb_first = i == n - 1 ? 1 : 0;
+    LPC_OK(gd_bwd_rows(e, 1, a));
+    LPC_OK(conv_middle(e, e->S2, e->P, true, g.sh, g.sh + g.H, true));       // D(Hg)
+    if (i > 0) head_of(i - 1);
+    a.tail = i == 0 ? 1 : 0;
+    LPC_OK(gd_bwd_rows(e, 2, a));
+  }
+  e->gd_fwd_done = false;     // S no longer holds the row spectra of the iterate
+  LPC_OK(launch_k(e, -1, k_gd_bwd_finish<256>, dim3(C + 1, n), 256, gd_bwd_red_bytes<256>(), (const double*)e->tape_part,
+                  e->P, rows, C, (const real*)e->galpha_sched, grad_alpha, grad_coef));
+  if (grad_init) LPC_OK(planar_to_hwc(e, a.gz, grad_init, e->cfg.batch, g.H, g.W, g.W, g.uplane, 0, 0, 0));
+  if (grad_data)
+    LPC_OK(launch_k(e, -1, k_gd_bwd_gdata<256>, grid1d(g.uplane, 256, e->cfg.batch), 256, 0, (const real*)a.gb, grad_data,
+                    (long)g.uplane, C, e->data_channels));
   return 0;
 }
 

@@ -6,6 +6,7 @@
 // constant, or the one launch of a kernel that only modules hold.  Nothing here is shape-specific source: the shape
 // arrives as macros.
 #include "lpc_gd_launch.h"
+#include "lpc_gd_bwd_launch.h"
 #include "lpc_gd_v2_kernels.h"
 
 #ifndef LPC_MOD_MID_PRE
@@ -102,6 +103,9 @@ static int m_gd_rows_update_fwd(Engine* e, const GdScalars* sc, const real* alph
                   geom_rev(e, e->plan.gd_rev_update),
                   row_arg(e), e->planW.tw, (const real2*)e->S2, e->S, e->gx, e->gaux, alpha, *sc);
 }
+static int m_gd_bwd_head(Engine* e, const GdBwd* a) { return launch_gd_bwd_half<0, RNT, REM, RSK>(e, row_arg(e), *a); }
+static int m_gd_bwd_mid(Engine* e, const GdBwd* a) { return launch_gd_bwd_half<1, RNT, REM, RSK>(e, row_arg(e), *a); }
+static int m_gd_bwd_update(Engine* e, const GdBwd* a) { return launch_gd_bwd_half<2, RNT, REM, RSK>(e, row_arg(e), *a); }
 #endif
 #endif   // half rows
 
@@ -202,6 +206,9 @@ extern "C" int lpc_module_init(LpcModule* m, size_t engine_size, const char* src
   m->gd_rows_mid = m_gd_rows_mid;
   m->gd_rows_update = m_gd_rows_update;
   m->gd_rows_update_fwd = m_gd_rows_update_fwd;
+  m->gd_bwd_head = m_gd_bwd_head;
+  m->gd_bwd_mid = m_gd_bwd_mid;
+  m->gd_bwd_update = m_gd_bwd_update;
 #endif
 #if LPC_MOD_PASSA
   m->cols_passA = m_cols_passA;

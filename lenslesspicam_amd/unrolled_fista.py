@@ -1,61 +1,168 @@
 """
-Unrolled FISTA *inference* on the MI355X engine: the iterations of the reference's ``UnrolledFISTA``
+Unrolled FISTA on the MI355X engine: the iterations of the reference's ``UnrolledFISTA``
 (``lensless/recon/unrolled_fista.py:18-106``) with per-iteration, per-channel steps ``alpha[i][c]`` and a
-``t_k`` sequence, on batches -- without autograd and the pre/post-processor networks.
+``t_k`` sequence, on batches -- inference and training.
+
+``UnrolledFISTA`` is a ``torch.nn.Module`` like the reference's: ``_alpha_p`` (``(n_iter, C)``) and, with
+``learn_tk``, ``_tk_p`` (``n_iter + 1``) are ``nn.Parameter`` s on the PSF's device, under the reference's names, so
+``state_dict()`` round-trips with its checkpoints.  ``forward(batch)`` with autograd enabled and any of the parameters,
+``batch`` or the initial estimate requiring a gradient runs as one ``torch.autograd.Function``: the forward is the
+inference launch sequence with the handle recording its tape (``lpc_fista_record``), the backward one reverse sweep in
+fused HIP kernels (``lpc_fista_backward``, csrc/lpc_gd_bwd_kernels.h) plus the chain through ``abs`` and
+``(t_i - 1) / t_{i+1}`` on ``n_iter``-sized tensors.  There is one tape per solver: ``backward()`` after a later
+``forward()`` of the same object raises; a forward without gradients in between keeps the tape's memory
+(``release_tape()`` gives it back).  Not differentiated (``NotImplementedError``, from ``backward()`` for the first two):
+``depth > 1``, frames whose padded height or width is odd, ``proj`` other than ``non_neg``; the PSF gets no gradient.
+
+Pre- / post-processor networks are not taken by the constructor: the measurement gets a gradient, so compose them in
+torch around ``forward()`` -- ``post(rec(pre(batch)))`` trains all three.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from .gd import FISTA, non_neg
 
 
-class UnrolledFISTA(FISTA):
-    def __init__(self, psf, n_iter=5, dtype=None, proj=non_neg, learn_tk=True, tk=1, **kwargs):
+class _UnrolledFISTAFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rec, batch, alpha_p, tk_p, init):
+        out = rec._run(batch, record=True, push_init=init is not None)
+        ctx.rec, ctx.gen = rec, rec._tape_gen
+        ctx.batch_meta = (tuple(batch.shape), batch.dtype, batch.device)
+        ctx.init_meta = None if init is None else (tuple(init.shape), init.dtype, init.device)
+        ctx.save_for_backward(alpha_p, tk_p)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        rec = ctx.rec
+        alpha_p, tk_p = ctx.saved_tensors
+        if int(rec._psf_shape[0]) > 1:
+            raise NotImplementedError("UnrolledFISTA.backward: depth > 1 is not implemented")
+        if rec._padded_shape[1] % 2 or rec._padded_shape[2] % 2:
+            raise NotImplementedError(
+                f"UnrolledFISTA.backward: padded frame {rec._padded_shape[1]} x {rec._padded_shape[2]} has an odd "
+                "length (convolve and deconvolve are not each other's adjoints there)")
+        if ctx.gen != rec._tape_gen:
+            raise RuntimeError("UnrolledFISTA.backward: tape overwritten by a later forward() of the same solver")
+        h, n, C = rec._handle, rec._n_iter, int(rec._psf_shape[3])
+        need_b, need_a, need_t, need_i = ctx.needs_input_grad[1:5]
+        g = rec._to_dev(grad_out)
+        bshape = ctx.batch_meta[0]
+        g_data = rec._empty((bshape[0],) + bshape[2:]) if need_b else None
+        g_init = rec._empty(tuple(g.shape)) if need_i else None
+        g_a, g_c = rec._empty((n, C)), rec._empty((n,))
+        h.fista_backward(g.data_ptr(), None if g_data is None else g_data.data_ptr(), g_a.data_ptr(), g_c.data_ptr(),
+                         None if g_init is None else g_init.data_ptr(), rec._stream())
+        # through |.| and c_i = (t_i - 1) / t_{i+1}, formed as _push_schedule forms them
+        with torch.enable_grad():
+            ap = alpha_p.detach().requires_grad_(need_a)
+            tp = tk_p.detach().requires_grad_(need_t)
+            alpha, coef = rec._schedule_of(ap, tp)
+            ga = torch.autograd.grad(alpha, ap, g_a.to(device=alpha.device, dtype=alpha.dtype))[0] if need_a else None
+            gt = torch.autograd.grad(coef, tp, g_c.to(device=coef.device, dtype=coef.dtype))[0] if need_t else None
+        gb = gi = None
+        if need_b:
+            gb = g_data[:, None].to(device=ctx.batch_meta[2], dtype=ctx.batch_meta[1])
+        if need_i:
+            shape, dtype, device = ctx.init_meta
+            gi = g_init if shape[0] == g_init.shape[0] else g_init.sum(0, keepdim=True)     # one estimate for the batch
+            gi = gi.reshape(shape).to(device=device, dtype=dtype)
+        return None, gb, ga, gt, gi
+
+
+class UnrolledFISTA(FISTA, torch.nn.Module):
+    def __init__(self, psf, n_iter=5, dtype=None, proj=non_neg, learn_tk=True, tk=1, skip_unrolled=False, **kwargs):
         assert isinstance(psf, torch.Tensor), "UnrolledFISTA takes torch tensors, like the reference"
+        torch.nn.Module.__init__(self)
         super().__init__(psf, dtype=dtype, proj=proj, tk=float(tk), n_iter=n_iter, **kwargs)
         C = int(self._psf_shape[3])
+        self.skip_unrolled = skip_unrolled
         # unrolled_fista.py:60-72: alpha initialised to 1.8 / max|H* H| per channel, for every iteration
         a0 = torch.as_tensor(np.asarray(self._alpha if not isinstance(self._alpha, torch.Tensor)
                                         else self._alpha.cpu().numpy(), dtype=np.float32))
-        self._alpha_p = torch.ones(n_iter, C, dtype=torch.float32) * a0
+        alpha = (torch.ones(n_iter, C, dtype=torch.float32) * a0).to(device=psf.device, dtype=self._tdtype)
         tks = [float(tk)]                                     # unrolled_fista.py:75-78
         for i in range(n_iter):
             tks.append((1 + np.sqrt(1 + 4 * tks[i] ** 2)) / 2)
-        self._tk_p = torch.Tensor(tks)
-        self._sched_dirty = True
+        tk_p = torch.Tensor(tks).to(psf.device)
+        # unrolled_fista.py:64-80: parameters unless skip_unrolled; t_k only when it is learnt
+        self._alpha_p = alpha if skip_unrolled else torch.nn.Parameter(alpha)
+        self._tk_p = torch.nn.Parameter(tk_p) if learn_tk and not skip_unrolled else tk_p
+        self._sched_key = None
+        self._tape_gen = 0
+        self._rec_state = (None, False)
 
     def set_parameters(self, alpha=None, tk=None):
-        self._sched_dirty = True
-        if alpha is not None:
-            a = torch.as_tensor(np.asarray(alpha, dtype=np.float32))
-            assert tuple(a.shape) == tuple(self._alpha_p.shape)
-            self._alpha_p = a
-        if tk is not None:
-            t = torch.as_tensor(np.asarray(tk, dtype=np.float32)).flatten()
-            assert t.numel() == self._n_iter + 1
-            self._tk_p = t
+        with torch.no_grad():
+            if alpha is not None:
+                a = torch.as_tensor(np.asarray(alpha, dtype=np.float32))
+                assert tuple(a.shape) == tuple(self._alpha_p.shape)
+                self._alpha_p.copy_(a)
+            if tk is not None:
+                t = torch.as_tensor(np.asarray(tk, dtype=np.float32)).flatten()
+                assert t.numel() == self._n_iter + 1
+                self._tk_p.copy_(t)
 
     def load_state_dict(self, state, strict=False):
         self.set_parameters(alpha=state["_alpha_p"].detach().cpu().numpy() if "_alpha_p" in state else None,
                             tk=state["_tk_p"].detach().cpu().numpy() if "_tk_p" in state else None)
 
+    def _schedule_of(self, alpha_p, tk_p):
+        """(alpha, coef) as the handle gets them: alpha in the solver's precision, coef in float32 arithmetic like
+        unrolled_fista.py:104 (the reference keeps ``_tk_p`` in float32 whatever the dtype)"""
+        alpha = torch.abs(alpha_p).to(self._tdtype)            # unrolled_fista.py:98-100 (positivity)
+        tk = torch.abs(tk_p).to(torch.float32)
+        return alpha, (tk[:-1] - 1) / tk[1:]
+
     def _push_schedule(self):
         """Hands the schedule to the handle -- only when the parameters changed or the handle is new (an upload
         is a blocking host -> device copy; ``forward()`` calls ``reset()`` for every batch)."""
-        if getattr(self, "_pushed_to", None) is self._handle and not self._sched_dirty:
+        key = (self._handle, self._alpha_p, self._alpha_p._version, self._tk_p, self._tk_p._version)
+        if self._sched_key is not None and len(key) == len(self._sched_key) and \
+                all(a is b if isinstance(a, torch.Tensor) else a == b for a, b in zip(key, self._sched_key)):
             return
-        alpha = torch.abs(self._alpha_p).to(torch.float32)     # unrolled_fista.py:98-100 (positivity)
-        tk = torch.abs(self._tk_p).to(torch.float32)
-        coef = (tk[:-1] - 1) / tk[1:]                           # float32 arithmetic, like :104
+        with torch.no_grad():
+            alpha, coef = self._schedule_of(self._alpha_p, self._tk_p)
         self._handle.set_fista_schedule(alpha.tolist(), coef.tolist(), self._stream())
-        self._pushed_to, self._sched_dirty = self._handle, False
+        self._sched_key = key
 
     def reset(self, tk=None, batch_size=None):
         if getattr(self, "_alpha_p", None) is not None:
             self._push_schedule()
         super().reset()
+
+    def _record(self, on):
+        """the handle records its tape from the next reset on, or stops: a forward without gradients between two
+        training steps pauses the recording and keeps the tape's memory (no wait for the stream, no allocation)"""
+        state = (self._handle, bool(on))
+        if on or self._rec_state[0] is self._handle:      # (a handle that never recorded has nothing to pause)
+            if state != self._rec_state:
+                self._handle.fista_record(1 if on else -1)
+                self._rec_state = state
+
+    def release_tape(self):
+        """gives the tape's device memory back (it returns with the next forward that needs gradients)"""
+        if self._rec_state[0] is self._handle:
+            self._handle.fista_record(0)
+        self._rec_state = (None, False)
+        self._tape_gen += 1
+
+    def _run(self, batch, record=False, push_init=False):
+        self._data = batch
+        self._upload_data()
+        if push_init:
+            self._push_initial_estimate()      # the current values of an estimate that is being learnt
+        self._tape_gen += 1            # reset() starts the tape over: gradients of earlier forwards are gone
+        self._push_schedule()
+        self._record(record)
+        self.reset()
+        self._iterate(self._n_iter)
+        return self._form_image()
 
     def forward(self, batch, psfs=None, background=None):
         """``batch``: (B, D, H, W, C) -> (B, D, H, W, C) after exactly ``n_iter`` unrolled iterations."""
@@ -64,8 +171,12 @@ class UnrolledFISTA(FISTA):
             raise NotImplementedError("background subtraction networks are outside the hot path")
         if psfs is not None:
             self._set_psf(psfs)
-        self._data = batch
-        self._upload_data()
-        self.reset()
-        self._iterate(self._n_iter)
-        return self._form_image()
+        init = self._initial_est if isinstance(self._initial_est, torch.Tensor) else None
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad
+                                           for t in (batch, self._alpha_p, self._tk_p, init)):
+            if self._hook:
+                raise NotImplementedError("UnrolledFISTA: only proj=non_neg is differentiated")
+            if init is not None and not init.requires_grad:
+                init = None
+            return _UnrolledFISTAFunction.apply(self, batch, self._alpha_p, self._tk_p, init)
+        return self._run(batch)
