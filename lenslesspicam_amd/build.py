@@ -1,8 +1,8 @@
 """Builds the product library in-tree: hipcc, gfx950 only.  (No JIT cache outside the tree: the .so files must travel
 with the source snapshot to the GPU box.)
 
-The engine is split into translation units (csrc/lpc_engine.h) so that the device compiler works on them in
-parallel: every ``csrc/*.cpp`` except ``lpc_module.cpp`` is compiled to an object file per flavour (float32, and
+The engine is split into translation units by role (the unit map at the top of csrc/lpc_engine.h) so that the device
+compiler works on them in parallel: every ``csrc/*.cpp`` except ``lpc_module.cpp`` is compiled to an object file per flavour (float32, and
 float64 with ``-DLPC_DOUBLE``), all jobs side by side, then linked into ``_lib/liblpc.so`` / ``_lib/liblpc_f64.so``.
 No relocatable device code is needed: a kernel is always launched from the unit that instantiates it.
 

@@ -77,28 +77,28 @@ int admm_cols(Engine* e, const AdmmScalars& sc) {
                                sc.skipa ? sc.mu1 * (real)g.Wp : (real)0.));
   {
     ColPass cp = e->passB;
-    cp.ga = e->g_sep ? e->Ga : nullptr;
-    cp.gb = e->g_sep ? e->Gb : nullptr;
+    cp.ga = e->admm.g_sep ? e->admm.Ga : nullptr;
+    cp.gb = e->admm.g_sep ? e->admm.Gb : nullptr;
     cp.rev = e->plan.rev_mid ? 1 : 0;
     cp.swz = e->plan.mid_swz;
     const AdmmMid mid = e->plan.admm_mid;
     if (mid == ADMM_MID_REG24) {
       LPC_OK(launch_k(e, LPC_K_COL_MID, k_cols_mid_admm_reg<8, 3>, dim3((g.Wc + 63) / 64, cp.G, e->P), 64, 0, g, e->planB,
-                      cp, e->S, spec_b(e), (const real2*)e->Hs, (const real*)e->Gabs, (const real2*)e->phr,
+                      cp, e->S, spec_b(e), (const real2*)e->Hs, (const real*)e->admm.Gabs, (const real2*)e->phr,
                       (const real2*)e->phc, sc.mu1, sc.mu2, sc.mu3, inv_points(g)));
     } else if (mid == ADMM_MID_MODULE) {   // compile-time plan in LDS: both spectra side by side, or one at a time
-      if (e->midc && !(e->midc_valid && e->midc_par[0] == (double)sc.mu1 && e->midc_par[1] == (double)sc.mu2 &&
-                       e->midc_par[2] == (double)sc.mu3)) {      // k_mid_consts: once per (PSF, step sizes)
+      if (e->admm.midc && !(e->admm.midc_valid && e->admm.midc_par[0] == (double)sc.mu1 && e->admm.midc_par[1] == (double)sc.mu2 &&
+                       e->admm.midc_par[2] == (double)sc.mu3)) {      // k_mid_consts: once per (PSF, step sizes)
         const long n = (long)((g.Hp + 1) & ~1) * g.cpitch;
         auto consts = [&](auto kernel) {
-          return launch_k(e, -1, kernel, grid1d(n, 256, e->Ppsf), 256, 0, (const real2*)e->Hs_t, (const real*)e->Gabs_t,
+          return launch_k(e, -1, kernel, grid1d(n, 256, e->Ppsf), 256, 0, (const real2*)e->admm.Hs_t, (const real*)e->admm.Gabs_t,
                           cp.ga, cp.gb, (const real2*)e->phr, (const real2*)e->phc, g.Hp, g.Wc, g.cpitch, g.cplane, sc.mu1,
-                          sc.mu2, sc.mu3, inv_points(g), e->midc, e->midrd);
+                          sc.mu2, sc.mu3, inv_points(g), e->admm.midc, e->admm.midrd);
         };
         if (e->plan.spec.mid_pc == 2) LPC_OK(consts(k_mid_consts<256, true>));
         else LPC_OK(consts(k_mid_consts<256, false>));
-        e->midc_par[0] = (double)sc.mu1; e->midc_par[1] = (double)sc.mu2; e->midc_par[2] = (double)sc.mu3;
-        e->midc_valid = true;
+        e->admm.midc_par[0] = (double)sc.mu1; e->admm.midc_par[1] = (double)sc.mu2; e->admm.midc_par[2] = (double)sc.mu3;
+        e->admm.midc_valid = true;
       }
       LPC_OK(e->mod->admm_mid(e, &cp, &sc, (sc.skipa && !split) ? sc.mu1 * (real)g.Wp : (real)0.));
     } else if (mid == ADMM_MID_RT_512X18) {

@@ -2,17 +2,24 @@
 // workgroup-shape dispatchers, the host functions that cross translation units, and the launches of the kernels that
 // the library and its plan modules both hold (lpc_launch.h; the gradient-descent family's: lpc_gd_launch.h).
 //
-// The library is split so that the device compiler works on several units in parallel:
-//   lpc_engine.cpp  plans, geometry, HBM workspace, the C ABI, the image-domain ADMM kernels, set-up / layout /
-//                   evaluation / preparation kernels
-//   lpc_rows.cpp    every row-pass launch (real <-> half-spectrum transforms, incl. the fused ADMM rows)
-//   lpc_cols.cpp    every column-pass launch (pass A, the fused middles)
+// One unit per role; the device compiler works on them in parallel, and a kernel is launched from the unit that
+// instantiates it:
+//   lpc_abi.cpp      the C ABI of include/lpc.h: argument checks, the call's stream, dispatch by algorithm, life cycle,
+//                    profile read-out.  No kernel launch, no arithmetic of the method
+//   lpc_planner.cpp  the option-driven rule table: frame geometry and the launch plan.  Nothing on the device
+//   lpc_setup.cpp    twiddles and plans, geometry set-up, the common workspace, PSF spectrum, the bare operator, and the
+//                    host helpers every algorithm shares with their layout / fill / min-max kernels
+//   lpc_admm.cpp     ADMM: host sequences and every image-domain ADMM kernel
+//   lpc_gd_host.cpp  the gradient-descent family: host sequences, the tape and the reverse sweep
+//   lpc_eval.cpp     evaluation reductions and the handle-free raw-frame / resize paths
+//   lpc_rows.cpp     every row-pass launch (real <-> half-spectrum transforms, incl. the fused ADMM rows)
+//   lpc_cols.cpp     every column-pass launch (pass A, the fused middles)
 //   lpc_gd.cpp, lpc_gd_update.cpp, lpc_gd_update_p0.cpp, lpc_gd_update_p1.cpp   the gradient-descent family's fused row
-//                   kernels (the update rows in three units: half-length rows, paired rows without / with the folded
-//                   radix-2 stage)
-//   lpc_gd_bwd.cpp  reverse mode of unrolled FISTA: the fused row kernels of lpc_fista_backward
-//   lpc_jit.cpp     plan modules: find / compile / load (lpc_plan.h)
-//   lpc_module.cpp  NOT part of the library: the source of a plan module (compile-time-plan kernels of one frame shape)
+//                    kernels (the update rows in three units: half-length rows, paired rows without / with the folded
+//                    radix-2 stage)
+//   lpc_gd_bwd.cpp   reverse mode of unrolled FISTA: the fused row kernels of lpc_fista_backward
+//   lpc_jit.cpp      plan modules: find / compile / load (lpc_plan.h)
+//   lpc_module.cpp   NOT part of the library: the source of a plan module (compile-time-plan kernels of one frame shape)
 #pragma once
 #include "lpc_kernels.h"
 #include "lpc.h"
@@ -91,7 +98,7 @@ enum AdmmK1 { ADMM_K1_ROWS, ADMM_K1_TV_W, ADMM_K1_TILED, ADMM_K1_SCALAR };
 enum AdmmMid { ADMM_MID_REG24, ADMM_MID_MODULE, ADMM_MID_RT_512X18, ADMM_MID_RT_LDS };
 
 // The launch plan of a handle: every kernel, tile shape, block order and fusion it runs, decided once at lpc_create
-// (lpc_engine.cpp: choose_plan, finish_plan).  The launch code reads this record and nothing else of the options.
+// (lpc_planner.cpp: choose_plan, finish_plan).  The launch code reads this record and nothing else of the options.
 struct LaunchPlan {
   // -- choose_plan: what the plan module's key needs
   PlanSpec spec;           // the compile-time-plan kernels this handle runs (lpc_plan.h)
@@ -116,32 +123,24 @@ struct LaunchPlan {
   bool g_terms = false;    // ADMM middles read |PsiT Psi| as row + column terms when it separates (EngineOpts::g_plane)
 };
 
-struct lpc_engine {
-  lpc_config cfg{};
-  PlaneGeom g{};
-  Fft1dPlan planW{}, planA{}, planB{};
-  Fft1dPlan planWi{};   // inverse-row plan with the radix-2 stage FIRST (rows_r2 only)
-  Fft1dPlan planWh{};   // length Wp/2: ADMM rows, one real row per half-length transform (rows_half)
-  EngineOpts opt;          // lpc_config::options, as parsed (read by the plan functions and lpc_jit.cpp only)
-  LaunchPlan plan;
-  const struct LpcModule* mod = nullptr;   // the loaded plan module that holds plan.spec's kernels (null: run-time plans only)
-  std::string mod_note;    // why there is no module, for lpc_plan_info
-  bool rows_r2 = false; // row plans end in a radix-2 stage: fold it into the Hermitian (un)tangling
-  ColPass passA{}, passB{};
-  int P = 0, Ppsf = 0, Pdata = 0;
-  std::vector<void*> allocs;
-  size_t total_bytes = 0;
+// what a launch needs: the call's stream and the optional event bracketing.  A handle is one; the handle-free entry
+// points (lpc_eval.cpp) make one of their own
+struct LaunchCtx {
+  KernelTimer timer;
+  lpcStream_t stream = nullptr;
+};
 
-  // spectral constants
-  real2* Hs = nullptr;     // [Ppsf] PSF spectrum, permuted row order, norm applied
-  real2* Hs_t = nullptr;   // ... and |G| below: copies in the pair-line layout for the module's 8-column middle (PlaneGeom::slay)
+// ADMM: state (padded real planes) and constants
+struct AdmmState {
+  // copies of the PSF spectrum and |G| in the pair-line layout for the module's 8-column middle (PlaneGeom::slay)
+  real2* Hs_t = nullptr;
   real* Gabs_t = nullptr;
   // ... and the sequential middle's point-wise constants, precombined per (PSF, step sizes) (lpc_kernels.h: k_mid_consts)
   void* midc = nullptr;       // MidConst (mid_pc 1) or real2 (mid_pc 2: real phases) per element
   real* midrd = nullptr;
   double midc_par[3] = {0, 0, 0};   // the step sizes the tables were made for
   bool midc_valid = false;
-  real* Gabs = nullptr;    // ADMM: |PsiT Psi| spectrum, ONE plane (identical for every channel)
+  real* Gabs = nullptr;    // |PsiT Psi| spectrum, ONE plane (identical for every channel)
   // ... and, when that plane is a sum of a row term and a column term (the reference's finite-difference gram is:
   // (2 - 2 cos th_r) + (2 - 2 cos th_c)), the two vectors the middles read instead of it: Ga[row] + Gb[col]
   real* Ga = nullptr;      // [Hp], the engine's (permuted) spectrum row order
@@ -150,13 +149,6 @@ struct lpc_engine {
   int g_sep = 0;
   std::vector<double> sched[4];  // optional per-iteration mu1, mu2, mu3, tau (unrolled ADMM)
   double last_par[4] = {0, 0, 0, 0};  // parameters of the most recent iteration
-  real2* phr = nullptr;    // [Hp] ifftshift phase, stored row order
-  real2* phc = nullptr;    // [Wc]
-  real2* twH = nullptr;
-  real2* tws_row = nullptr;   // stage twiddles of the module's row plan in lane order (lpc_sfft.h: SPlan::tws_off)
-  // work spectra: [2][P] planes (ADMM uses both halves, others the first)
-  real2* S = nullptr;
-  // ADMM state (padded real planes)
   real *V[2] = {nullptr, nullptr}, *HVb[2] = {nullptr, nullptr}, *xi = nullptr, *rho = nullptr,
         *Rsp = nullptr, *Aarr = nullptr;
   real *eta0[2] = {nullptr, nullptr}, *eta1[2] = {nullptr, nullptr};  // ping-pong (halo reads)
@@ -165,18 +157,30 @@ struct lpc_engine {
   // sees that clamped copy, and it is a pure function of V: vw_cur = the next iteration's W sees clamp(V),
   // vw_old = the previous iteration's W saw clamp(V_old) (needed to recompute W_old) -- AdmmScalars::clamp_cur / _old
   bool vw_cur = false, vw_old = false;
-  // GD family state (un-padded planes)
+  // plug-and-play ADMM (lpc_admm_pnp_begin / _end): explicit state in the arrays the fused path uses for the TV duals
+  //   eta0[0] = eta, eta1[0] = U, eta0[1] = X, eta1[1] = W   (all image-shaped)
+  bool pnp_mode = false, pnp_pending = false;
+};
+
+// gradient-descent family: state (un-padded planes)
+struct GdState {
   real *gx = nullptr, *gaux = nullptr;  // x and (p | xk_prev)
   real* galpha = nullptr;               // [C] device
   real* gx0 = nullptr;                  // [C] default start value per channel
   real2* S2 = nullptr;                  // second spectrum buffer (row-inverse+forward is out of place)
   double tk = 1.0, nest_mu = 0.9, nest_p = 0.0;
-  // unrolled FISTA (unrolled_fista.py:91-106): per-iteration step alpha[i][c] and momentum factor coef[i]
-  std::vector<real> fista_coef;
+  bool fwd_done = false;       // the row spectra of H x's input are already in S (written by the fused update kernel)
+  bool split_pending = false;  // lpc_iterate_begin ran, lpc_iterate_end has not yet
+};
+
+// unrolled FISTA (unrolled_fista.py:91-106): per-iteration step alpha[i][c] and momentum factor coef[i], and the tape of
+// the reverse mode
+struct FistaSchedule {
+  std::vector<real> coef;
   real* galpha_sched = nullptr;  // device [n][C]
-  size_t galpha_sched_cap = 0;   // elements allocated for it (re-used by later schedules that fit)
-  int fista_sched_n = 0;
-  std::vector<real> fista_alpha;   // host copy of the schedule's alpha (lpc_fista_backward refuses a zero step)
+  size_t sched_cap = 0;          // elements allocated for it (re-used by later schedules that fit)
+  int sched_n = 0;
+  std::vector<real> alpha;       // host copy of the schedule's alpha (lpc_fista_backward refuses a zero step)
   // reverse mode (lpc_fista_record / lpc_fista_backward): the tape is ONE allocation of (2 n + 4) un-padded state arrays
   //   y_0 .. y_n | xk_0 .. xk_{n-1} | work: gy / gz, carry, g_b      (y_i = gx before iteration i, xk_i = gaux after it)
   // and the per-row partial sums of g_coef / g_alpha: n * P * H * 2 doubles
@@ -185,20 +189,41 @@ struct lpc_engine {
   double* tape_part = nullptr;
   int tape_n = 0;              // iterations the tape was allocated for
   long tape_iters = -1;        // iterations recorded since the last reset (-1: nothing recorded)
-  int data_channels = 0;       // of the last lpc_set_data
-  // common
+};
+
+struct lpc_engine : LaunchCtx {
+  lpc_config cfg{};
+  PlaneGeom g{};
+  Fft1dPlan planW{}, planA{}, planB{};
+  Fft1dPlan planWi{};   // inverse-row plan with the radix-2 stage FIRST (rows_r2 only)
+  Fft1dPlan planWh{};   // length Wp/2: ADMM rows, one real row per half-length transform (rows_half)
+  EngineOpts opt;          // lpc_config::options, as parsed (read by the planner and lpc_jit.cpp only)
+  LaunchPlan plan;
+  const struct LpcModule* mod = nullptr;   // the loaded plan module that holds plan.spec's kernels (null: run-time plans only)
+  std::string mod_note;    // why there is no module, for lpc_plan_info
+  bool rows_r2 = false; // row plans end in a radix-2 stage: fold it into the Hermitian (un)tangling
+  ColPass passA{}, passB{};
+  int P = 0, Ppsf = 0, Pdata = 0;
+  std::vector<std::pair<void*, size_t>> allocs;   // every device allocation of the handle and its bytes (dev_alloc / dev_free)
+  size_t total_bytes = 0;
+
+  real2* Hs = nullptr;     // [Ppsf] PSF spectrum, permuted row order, norm applied
+  real2* phr = nullptr;    // [Hp] ifftshift phase, stored row order
+  real2* phc = nullptr;    // [Wc]
+  real2* twH = nullptr;
+  real2* tws_row = nullptr;   // stage twiddles of the module's row plan in lane order (lpc_sfft.h: SPlan::tws_off)
+  // work spectra: [2][P] planes (ADMM uses both halves, others the first)
+  real2* S = nullptr;
   real* Y = nullptr;         // data planes, un-padded [Pdata][H][W]
+  int data_channels = 0;     // of the last lpc_set_data
   real* init_est = nullptr;  // planar copy of the initial estimate (or null)
   real* psf_planar = nullptr;
+  real *conv_in = nullptr, *conv_out = nullptr;   // LPC_ALGO_CONV: staging planes of the channels-last <-> planar hop
   bool has_init = false, psf_set = false, data_set = false, first = true;
-  bool gd_fwd_done = false;    // the row spectra of H x's input are already in S (written by the fused update kernel)
-  bool split_pending = false;  // lpc_iterate_begin ran, lpc_iterate_end has not yet
-  // plug-and-play ADMM (lpc_admm_pnp_begin / _end): explicit state in the arrays the fused path uses for the TV duals
-  //   eta0[0] = eta, eta1[0] = U, eta0[1] = X, eta1[1] = W   (all image-shaped)
-  bool pnp_mode = false, pnp_pending = false;
   long iters_done = 0;
-  KernelTimer timer;
-  lpcStream_t stream = nullptr;
+  AdmmState admm;
+  GdState gd;
+  FistaSchedule fista;
 };
 typedef lpc_engine Engine;
 
@@ -207,20 +232,32 @@ static inline int dev_alloc(Engine* e, Tp** out, size_t count) {
   void* p = nullptr;
   size_t bytes = count * sizeof(Tp);
   LPC_RT(rt::dev_malloc(&p, bytes));
-  e->allocs.push_back(p);
+  e->allocs.push_back({p, bytes});
   e->total_bytes += bytes;
   *out = (Tp*)p;
   return 0;
 }
+// gives one allocation of the handle back once the stream has drained (null: nothing to do)
+static inline void dev_free(Engine* e, void* p) {
+  if (!p) return;
+  (void)rt::stream_sync(e->stream);
+  for (auto it = e->allocs.begin(); it != e->allocs.end(); ++it)
+    if (it->first == p) {
+      e->total_bytes -= it->second;
+      e->allocs.erase(it);
+      break;
+    }
+  (void)rt::dev_free(p);
+}
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: the (device, function) pairs that have
-// it live in the CORE library (lpc_engine.cpp) -- launch_k is instantiated inside every plan module too, and a
+// it live in the CORE library (lpc_setup.cpp) -- launch_k is instantiated inside every plan module too, and a
 // thread_local set there would register a TLS destructor that pins the module: dlclose() would never unload it
 int big_smem_once(const void* fn, size_t smem);
 
 // generic launcher (+ optional event bracketing of hot-loop kernels)
 template <class K, class... A>
-static inline int launch_k(Engine* e, int kid, K kernel, dim3 grid, int nt, size_t smem, A... args) {
+static inline int launch_k(LaunchCtx* e, int kid, K kernel, dim3 grid, int nt, size_t smem, A... args) {
   if (smem > 48 * 1024) LPC_OK(big_smem_once((const void*)kernel, smem));
 #if !defined(LPC_SIMT_EMU)
   const bool timed = e->timer.on && kid >= 0 && ((e->timer.mask >> kid) & 1u);
@@ -301,7 +338,7 @@ struct LpcModule {
   int (*cols_passA)(Engine*, const ColPass*, real2* S, int nplanes, int inverse, int kid);
   int (*admm_mid)(Engine*, const ColPass*, const AdmmScalars*, real sb_outside_scale);
   int k1_rows;    // admm_rows_fwd_x takes the TV / W half of the image-domain work as well (k_rfwd_arrays_x<.., K1>)
-  int mid_pc;     // its sequential middle reads the precombined constants (Engine::midc / midrd)
+  int mid_pc;     // its sequential middle reads the precombined constants (AdmmState::midc / midrd)
   int slay;       // its ADMM row kernels and fused middle keep the work spectra in pair lines (PlanSpec::slay)
   int gd_v2;      // the module holds k_gd_resid_v2 / k_gd_update_fwd_v2 for its row plan (lpc_gd_v2_kernels.h)
 };
@@ -311,10 +348,67 @@ void release_plan_module(const LpcModule* mod);     // a handle that got a modul
 int build_plan_module(const PlanSpec& spec, const EngineOpts& opt, std::string* path_or_error);   // compile only (no load); no-op when the module is on disk
 
 // ---- host functions that cross translation units ------------------------------------------------------------
+// lpc_planner.cpp: frame geometry (rfft_convolve.py:110-117), plane counts and the launch plan of a configuration
+struct ShapePlan {
+  PlaneGeom g{};
+  int P = 0, Ppsf = 0, Pdata = 0;
+  LaunchPlan plan;
+  bool want_static = false;   // the frame is large enough for compile-time plans and the options allow them
+};
+int plan_cu_count();
+bool plan_radices(int n, std::vector<int>& rad);
+int setup_shape(const lpc_config& c, const EngineOpts& o, int cu, ShapePlan* out);
+void choose_plan(const lpc_config& c, const EngineOpts& o, const PlaneGeom& g, int P, bool allow_static, int cu, LaunchPlan* pl);
+void finish_plan(const lpc_config& c, const EngineOpts& o, const PlaneGeom& g, int P, const LpcModule* mod, bool lane_twiddles,
+                 int cu, LaunchPlan* pl);
+// lpc_setup.cpp
+int upload(Engine* e, void* dst, const void* src, size_t bytes);
+int setup_geometry(Engine* e);
+int alloc_common(Engine* e);                                    // PSF spectrum, work spectra, data / staging planes
+int set_psf(Engine* e, const real* dev_psf);
+int fft2_forward_setup(Engine* e, const RealSrc& src, real2* S, int nplanes);
+int convolve_planar(Engine* e, const real* xin, real* xout, int nplanes, bool padded_io, bool adjoint);
+int convolve_hwc(Engine* e, const real* dev_x, real* dev_out, int n, int x_channels, bool adjoint, bool spectrum);
+int hwc_to_planar(Engine* e, const real* src, real* dst, int nimg, int rows, int cols, int pitch, long dplane,
+                  int src_channels = 0);
+int planar_to_hwc(Engine* e, real* src, real* dst, int nimg, int rows, int cols, int pitch, long splane, int row0, int col0,
+                  int clamp);
+int planar2_to_hwc2(Engine* e, const real* a0, const real* a1, real* dst, int nimg);   // two padded arrays -> (.., 2)
+int check_channels(const Engine* e, int ch, const char* who);
+int fill_planar(Engine* e, real* p, long n, real v);
+int plane_minmax(Engine* e, const real2* Hs, const real* plane, int nblk, int nplanes, real* partial);   // k_plane_minmax
+// lpc_admm.cpp
+int admm_alloc(Engine* e);
+int admm_setup_constants(Engine* e);
+int admm_reset(Engine* e);
+int admm_iterate(Engine* e, int n_iter);
+int admm_pnp_begin(Engine* e, int use_dual, real* dev_denoiser_in);
+int admm_pnp_end(Engine* e, int use_dual, const real* dev_U);
+int admm_set_psi_gram(Engine* e, const real* dev_gabs);
+int admm_psi_step(Engine* e, const real* dev_psit);
+int admm_form_image(Engine* e, real* dev_out);
+int admm_get_state(Engine* e, const std::string& nm, real* dev_out);
+int admm_kernel_bytes(Engine* e, int kid, double* bytes);
+double admm_model_bytes(const Engine* e);
+// lpc_gd_host.cpp
+int gd_alloc(Engine* e);
+int gd_setup_constants(Engine* e);
+int gd_apply_momentum_reset(Engine* e);
+void gd_tape_free(Engine* e);
+int gd_tape_alloc(Engine* e);
+int gd_set_schedule(Engine* e, int n, const real* alpha, const real* coef);
+int gd_reset(Engine* e);
+int gd_iterate(Engine* e, int n_iter, int split = 0);
+int gd_finish_split(Engine* e, const real* dev_projected);
+int gd_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_alpha, real* grad_coef, real* grad_init);
+int gd_form_image(Engine* e, real* dev_out);
+int gd_get_state(Engine* e, const std::string& nm, real* dev_out);
+int gd_kernel_bytes(Engine* e, int kid, double* bytes);
+double gd_model_bytes(const Engine* e);
 // lpc_rows.cpp
 int rows_fwd_single(Engine* e, const RealSrc& src, real2* S, int nplanes, int kid);
 int rows_inv_single(Engine* e, const real2* S, const RealDst& dst, int nplanes, int kid);
-int admm_rows_fwd(Engine* e);                                   // e->Rsp, e->Aarr -> the two work spectra
+int admm_rows_fwd(Engine* e);                                   // e->admm.Rsp, e->admm.Aarr -> the two work spectra
 int admm_rows_inv(Engine* e, real* Vout, real* HVout, bool skip_hv_outside = false);          // the two work spectra -> V, H V
 // lpc_cols.cpp
 int cols_passA(Engine* e, real2* S, int nplanes, bool inverse, int zr0, int zr1, int kid, bool crop_rows_only = false,

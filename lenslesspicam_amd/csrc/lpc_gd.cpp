@@ -1,7 +1,7 @@
 // lpc_gd.cpp -- launches of the gradient-descent family's fused row kernels (see lpc_engine.h for the split)
 #include "lpc_gd_launch.h"
 
-// spectrum rows of H x (e->S) -> irfft -> shift + crop -> - y -> re-pad -> rfft -> spectrum rows (e->S2)
+// spectrum rows of H x (e->S) -> irfft -> shift + crop -> - y -> re-pad -> rfft -> spectrum rows (e->gd.S2)
 int gd_rows_mid(Engine* e) {
   const PlaneGeom& g = e->g;
   const int nblk = (g.H + 1) / 2;
@@ -15,6 +15,6 @@ int gd_rows_mid(Engine* e) {
     constexpr bool sk = decltype(SK)::value, r2 = decltype(R2)::value;
     return launch_k(e, LPC_K_ROW_INV, k_rinv_gd_mid<nt, em, sk, r2>, dim3(nblk, e->P), nt,
                     LPC_ROW_SMEM_BYTES(g.Wp, sk), g, e->planW, e->rows_r2 ? e->planWi : e->planW,
-                    (const real2*)e->S, e->S2, (const real*)e->Y);
+                    (const real2*)e->S, e->gd.S2, (const real*)e->Y);
   });
 }

@@ -21,11 +21,11 @@ int gd_bwd_rows(Engine* e, int mode, const GdBwd& a) {
     const size_t smem = gd_bwd_red_bytes<nt>() + LPC_ROW_SMEM_BYTES(g.Wp, sk);
     if (mode == 0)
       return launch_k(e, -1, k_gd_bwd_paired<0, nt, em, sk>, dim3(nblk, e->P), nt, smem, g, e->planW,
-                      (const real2*)e->S2, e->S, a);
+                      (const real2*)e->gd.S2, e->S, a);
     if (mode == 1)
       return launch_k(e, -1, k_gd_bwd_paired<1, nt, em, sk>, dim3(nblk, e->P), nt, smem, g, e->planW,
-                      (const real2*)e->S, e->S2, a);
+                      (const real2*)e->S, e->gd.S2, a);
     return launch_k(e, -1, k_gd_bwd_paired<2, nt, em, sk>, dim3(nblk, e->P), nt, smem, g, e->planW,
-                    (const real2*)e->S2, e->S, a);
+                    (const real2*)e->gd.S2, e->S, a);
   });
 }

@@ -4,12 +4,12 @@
 #include "lpc_engine.h"
 #include "lpc_gd_bwd_kernels.h"
 
-// MODE 0: head of the last iteration -> rows (e->S);  1: rows (e->S) -> Hg, g_b -> rows (e->S2);
-// 2: rows (e->S2) -> gy -> head of the iteration before (or the tail) -> rows (e->S).  pa: the plan of length Wp / 2
+// MODE 0: head of the last iteration -> rows (e->S);  1: rows (e->S) -> Hg, g_b -> rows (e->gd.S2);
+// 2: rows (e->gd.S2) -> gy -> head of the iteration before (or the tail) -> rows (e->S).  pa: the plan of length Wp / 2
 template <int MODE, int NT, int EM, int SK, class PA>
 static inline int launch_gd_bwd_half(Engine* e, const PA& pa, const GdBwd& a) {
   return launch_k(e, -1, k_gd_bwd_half<MODE, NT, EM, SK, PA>, dim3(e->g.H, e->P), NT,
                   gd_bwd_red_bytes<NT>() + LPC_ROW_SMEM_BYTES(e->g.Wp / 2, SK),
                   geom_rev(e, MODE == 1 ? e->plan.gd_rev_resid : e->plan.gd_rev_update), pa, e->planW.tw,
-                  (const real2*)(MODE == 1 ? e->S : e->S2), MODE == 1 ? e->S2 : e->S, a);
+                  (const real2*)(MODE == 1 ? e->S : e->gd.S2), MODE == 1 ? e->gd.S2 : e->S, a);
 }

@@ -1,5 +1,5 @@
 // lpc_gd_kernels.h -- kernels of the projected-gradient family (vanilla / Nesterov / FISTA)
-// and the small reductions of the set-up path.
+// and the per-channel finish / fill kernels of its set-up path (reductions: lpc_reduce_kernels.h).
 //
 // One GD iteration = grad = H^T (H x - y) followed by a momentum update and the
 // non-negativity projection (lensless/recon/gd.py:128-134,183-188,235-241).  The state is
@@ -316,90 +316,6 @@ __global__ __launch_bounds__(NT) void k_gd_post(PlaneGeom g, const real* LPC_RES
   }
 }
 
-// ---- reductions (set-up only): per-plane max/min with wavefront shuffles ---------------------
-template <int NT>
-static __device__ __forceinline__ void block_minmax(real& mx, real& mn, real* scratch, int tid) {
-#if !defined(LPC_SIMT_EMU)
-  for (int off = 32; off > 0; off >>= 1) {  // 64-lane wavefront
-    mx = rmax(mx, __shfl_down(mx, off, 64));
-    mn = rmin(mn, __shfl_down(mn, off, 64));
-  }
-  const int wave = tid >> 6, lane = tid & 63;
-  if (lane == 0) { scratch[2 * wave] = mx; scratch[2 * wave + 1] = mn; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < NT / 64; ++w) { mx = rmax(mx, scratch[2 * w]); mn = rmin(mn, scratch[2 * w + 1]); }
-  }
-#else
-  scratch[2 * tid] = mx; scratch[2 * tid + 1] = mn;
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < NT; ++w) { mx = rmax(mx, scratch[2 * w]); mn = rmin(mn, scratch[2 * w + 1]); }
-  }
-#endif
-}
-
-// mode 0: values are |H* H| of a spectrum plane (pitch cpitch, Wc valid columns);
-// mode 1: values are an un-padded image plane.  Writes (max, min) per (plane, block).
-template <int NT>
-__global__ __launch_bounds__(NT) void k_plane_minmax(PlaneGeom g, const real2* LPC_RESTRICT Hs,
-                                                      const real* LPC_RESTRICT plane, int mode,
-                                                      real* LPC_RESTRICT partial) {
-  LPC_DYN_SMEM(smem);
-  real* scratch = (real*)smem;
-  const int tid = LPC_TID(NT);
-  const long pl = blockIdx.y;
-  real mx = -INFINITY, mn = INFINITY;
-  if (mode == 0) {
-    const long n = (long)g.Hp * g.Wc;
-    for (long e = (long)blockIdx.x * NT + tid; e < n; e += (long)gridDim.x * NT) {
-      const int r = (int)(e / g.Wc), c = (int)(e - (long)r * g.Wc);
-      const real2 h = Hs[pl * g.cplane + (long)r * g.cpitch + c];
-      const real a = h.x * h.x + h.y * h.y;
-      mx = rmax(mx, a); mn = rmin(mn, a);
-    }
-  } else {
-    const long n = g.uplane;
-    for (long e = (long)blockIdx.x * NT + tid; e < n; e += (long)gridDim.x * NT) {
-      const real a = plane[pl * g.uplane + e];
-      mx = rmax(mx, a); mn = rmin(mn, a);
-    }
-  }
-  block_minmax<NT>(mx, mn, scratch, tid);
-  if (tid == 0) {
-    partial[2 * (pl * gridDim.x + blockIdx.x)] = mx;
-    partial[2 * (pl * gridDim.x + blockIdx.x) + 1] = mn;
-  }
-}
-
-// ---- is a real spectrum plane G[r][c] the sum of a row term and a column term?  (ADMM set-up, ColPass::ga) -----
-// ga[r] = G[r][0], gb[c] = G[0][c] - G[0][0]
-static __global__ void k_gsep_extract(const real* LPC_RESTRICT G, int Hp, int Wc, long cpitch, real* LPC_RESTRICT ga,
-                                      real* LPC_RESTRICT gb) {
-  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < Hp) ga[e] = G[e * cpitch];
-  if (e < cpitch) gb[e] = e < Wc ? G[e] - G[0] : (real)0.;
-}
-// partial[2 b] = max |G - ga - gb|, partial[2 b + 1] = -max |G| over the block's share of the plane
-template <int NT>
-__global__ __launch_bounds__(NT) void k_gsep_check(const real* LPC_RESTRICT G, int Hp, int Wc, long cpitch,
-                                                    const real* LPC_RESTRICT ga, const real* LPC_RESTRICT gb,
-                                                    real* LPC_RESTRICT partial) {
-  LPC_DYN_SMEM(smem);
-  real* scratch = (real*)smem;
-  const int tid = LPC_TID(NT);
-  real mx = (real)0., mn = (real)0.;
-  const long n = (long)Hp * Wc;
-  for (long e = (long)blockIdx.x * NT + tid; e < n; e += (long)gridDim.x * NT) {
-    const int r = (int)(e / Wc), c = (int)(e - (long)r * Wc);
-    const real v = G[(long)r * cpitch + c];
-    mx = rmax(mx, rabs(v - (ga[r] + gb[c])));
-    mn = rmin(mn, -rabs(v));
-  }
-  block_minmax<NT>(mx, mn, scratch, tid);
-  if (tid == 0) { partial[2 * blockIdx.x] = mx; partial[2 * blockIdx.x + 1] = mn; }
-}
-
 // final per-channel combine over depth planes and blocks (gd.py:100-112 flatten (D,H,W) per channel):
 // mode 0: out[c] = lip_fact / max;  mode 1: out[c] = (max + min) / 2
 static __global__ void k_channel_finish(const real* LPC_RESTRICT partial, int nblk, int D, int C, int mode, real lip,
@@ -424,22 +340,4 @@ __global__ __launch_bounds__(NT) void k_fill_per_channel(real* LPC_RESTRICT x, l
   const real v = val[pl % C];
   for (long e = (long)blockIdx.x * NT + threadIdx.x; e < plane_elems; e += (long)gridDim.x * NT)
     x[pl * plane_elems + e] = v;
-}
-
-// two planar arrays (component 0 / 1) -> channels-last with a trailing axis of 2
-template <int NT>
-__global__ __launch_bounds__(NT) void k_planar2_to_hwc2(const real* LPC_RESTRICT a0, const real* LPC_RESTRICT a1,
-                                                         real* LPC_RESTRICT dst, int rows, int cols, int C,
-                                                         int pitch, long splane) {
-  const long n = (long)rows * cols * C;
-  const long img = blockIdx.y;
-  for (long e = (long)blockIdx.x * NT + threadIdx.x; e < n; e += (long)gridDim.x * NT) {
-    const int c = (int)(e % C);
-    const long rc = e / C;
-    const int col = (int)(rc % cols);
-    const int row = (int)(rc / cols);
-    const long so = (img * C + c) * splane + (long)row * pitch + col;
-    dst[(img * n + e) * 2 + 0] = a0[so];
-    dst[(img * n + e) * 2 + 1] = a1[so];
-  }
 }

@@ -8,7 +8,7 @@
 int gd_rows_update_paired_r2(Engine* e, const GdScalars& sc, const real* alpha);   // lpc_gd_update_p1.cpp
 int gd_rows_update_paired_plain(Engine* e, const GdScalars& sc, const real* alpha);   // lpc_gd_update_p0.cpp
 
-// spectrum rows of the gradient (e->S2) -> irfft -> shift + crop -> fused momentum / projection update of x
+// spectrum rows of the gradient (e->gd.S2) -> irfft -> shift + crop -> fused momentum / projection update of x
 int gd_rows_update(Engine* e, const GdScalars& sc, const real* alpha) {
   const PlaneGeom& g = e->g;
   if (e->mod && e->mod->gd_rows_update) return e->mod->gd_rows_update(e, &sc, alpha);

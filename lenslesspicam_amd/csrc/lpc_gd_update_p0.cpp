@@ -11,8 +11,8 @@ int gd_rows_update_paired_plain(Engine* e, const GdScalars& sc, const real* alph
     constexpr int nt = decltype(NTc)::value, em = decltype(EM)::value;
     if (pinv.skew_ok)
       return launch_k(e, LPC_K_SPATIAL, k_rinv_gd_update<nt, em, true, false>, dim3(nblk, e->P), nt,
-                      LPC_ROW_SMEM_BYTES(g.Wp, true), g, pinv, (const real2*)e->S2, e->gx, e->gaux, alpha, sc);
+                      LPC_ROW_SMEM_BYTES(g.Wp, true), g, pinv, (const real2*)e->gd.S2, e->gd.gx, e->gd.gaux, alpha, sc);
     return launch_k(e, LPC_K_SPATIAL, k_rinv_gd_update<nt, em, false, false>, dim3(nblk, e->P), nt,
-                    LPC_ROW_SMEM_BYTES(g.Wp, false), g, pinv, (const real2*)e->S2, e->gx, e->gaux, alpha, sc);
+                    LPC_ROW_SMEM_BYTES(g.Wp, false), g, pinv, (const real2*)e->gd.S2, e->gd.gx, e->gd.gaux, alpha, sc);
   });
 }

@@ -11,6 +11,6 @@ int gd_rows_update_paired_r2(Engine* e, const GdScalars& sc, const real* alpha) 
     constexpr int nt = decltype(NTc)::value, em = decltype(EM)::value;
     // (the inverse plan with the radix-2 stage first never keeps the LDS skew affine: planWi.skew_ok == 0)
     return launch_k(e, LPC_K_SPATIAL, k_rinv_gd_update<nt, em, false, true>, dim3(nblk, e->P), nt,
-                    LPC_ROW_SMEM_BYTES(g.Wp, false), g, pinv, (const real2*)e->S2, e->gx, e->gaux, alpha, sc);
+                    LPC_ROW_SMEM_BYTES(g.Wp, false), g, pinv, (const real2*)e->gd.S2, e->gd.gx, e->gd.gaux, alpha, sc);
   });
 }

@@ -2227,3 +2227,21 @@ template <int NT>
 __global__ __launch_bounds__(NT) void k_fill(real* LPC_RESTRICT p, long n, real v) {
   for (long e = (long)blockIdx.x * NT + threadIdx.x; e < n; e += (long)gridDim.x * NT) p[e] = v;
 }
+
+// two planar arrays (component 0 / 1) -> channels-last with a trailing axis of 2
+template <int NT>
+__global__ __launch_bounds__(NT) void k_planar2_to_hwc2(const real* LPC_RESTRICT a0, const real* LPC_RESTRICT a1,
+                                                         real* LPC_RESTRICT dst, int rows, int cols, int C,
+                                                         int pitch, long splane) {
+  const long n = (long)rows * cols * C;
+  const long img = blockIdx.y;
+  for (long e = (long)blockIdx.x * NT + threadIdx.x; e < n; e += (long)gridDim.x * NT) {
+    const int c = (int)(e % C);
+    const long rc = e / C;
+    const int col = (int)(rc % cols);
+    const int row = (int)(rc / cols);
+    const long so = (img * C + c) * splane + (long)row * pitch + col;
+    dst[(img * n + e) * 2 + 0] = a0[so];
+    dst[(img * n + e) * 2 + 1] = a1[so];
+  }
+}

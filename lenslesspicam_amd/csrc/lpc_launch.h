@@ -25,11 +25,11 @@ static inline int launch_rows_inv_half(Engine* e, const PA& pa, const real2* S, 
   return launch_k(e, kid, k_rinv_rows_half<NT, EM, SK, PA>, dim3(dst.nrows, nplanes), NT,
                   LPC_ROW_SMEM_BYTES(e->g.Wp / 2, SK), e->g, pa, e->planW.tw, S, dst);
 }
-// ADMM: e->Rsp, e->Aarr -> the two work spectra, and back to V, H V (skip_hv: H V on the rows of the sensor window alone)
+// ADMM: e->admm.Rsp, e->admm.Aarr -> the two work spectra, and back to V, H V (skip_hv: H V on the rows of the sensor window alone)
 template <int NT, int EM, int SK, class PA>
 static inline int launch_admm_rows_fwd_half(Engine* e, const PA& pa) {
   return launch_k(e, LPC_K_ROW_FWD, k_rfwd_half<NT, EM, SK, PA>, dim3(2 * e->g.Hp, e->P), NT,
-                  LPC_ROW_SMEM_BYTES(e->g.Wp / 2, SK), e->g, pa, e->planW.tw, (const real*)e->Rsp, (const real*)e->Aarr,
+                  LPC_ROW_SMEM_BYTES(e->g.Wp / 2, SK), e->g, pa, e->planW.tw, (const real*)e->admm.Rsp, (const real*)e->admm.Aarr,
                   e->S, spec_b(e));
 }
 template <int NT, int EM, int SK, class PA>
@@ -44,7 +44,7 @@ static inline int launch_admm_rows_inv_half(Engine* e, const PA& pa, real* Vout,
 template <int NT, int EM, int SK, bool R2, int SL, class PA>
 static inline int launch_admm_rows_fwd_paired(Engine* e, const PA& pa) {
   return launch_k(e, LPC_K_ROW_FWD, k_rfwd_arrays<NT, EM, SK, R2, PA, SL>, dim3(paired_rows_grid(e->g, false), e->P), NT,
-                  LPC_ROW_SMEM_BYTES(e->g.Wp, SK), e->g, pa, (const real*)e->Rsp, (const real*)e->Aarr, e->S, spec_b(e));
+                  LPC_ROW_SMEM_BYTES(e->g.Wp, SK), e->g, pa, (const real*)e->admm.Rsp, (const real*)e->admm.Aarr, e->S, spec_b(e));
 }
 template <int NT, int EM, int SK, bool R2, int SL, class PA>
 static inline int launch_admm_rows_inv_paired(Engine* e, const PA& pa, real* Vout, real* HVout, bool skip_hv) {
@@ -68,7 +68,7 @@ template <int NT, int EM, int SBT2, bool TWLDS, int SL, class PA>
 static inline int launch_admm_mid(Engine* e, const PA& pa, const ColPass& cp, const AdmmScalars& sc, real sb_outside_scale) {
   return launch_k(e, LPC_K_COL_MID, k_cols_mid_admm<NT, EM, PA, SBT2, TWLDS, SL>, dim3(cp.G * cp.ntile_c, e->P), NT,
                   (size_t)cp.N * (2 * cp.T + (TWLDS ? 1 : 0)) * sizeof(real2), e->g, pa, cp, e->S, spec_b(e),
-                  (const real2*)(SL ? e->Hs_t : e->Hs), (const real*)(SL ? e->Gabs_t : e->Gabs), (const real2*)e->phr,
+                  (const real2*)(SL ? e->admm.Hs_t : e->Hs), (const real*)(SL ? e->admm.Gabs_t : e->admm.Gabs), (const real2*)e->phr,
                   (const real2*)e->phc, make_fastdiv((unsigned)(2 * cp.T)), sc.mu1, sc.mu2, sc.mu3, inv_points(e->g),
                   sb_outside_scale);
 }

@@ -4,25 +4,7 @@
 // Memory-bound single passes; squares are accumulated in double (the reference sums float32 with
 // torch's pairwise tree, skimage averages in float64), results never leave the device.
 #pragma once
-#include "lpc_gd_kernels.h"
-
-template <int NT>
-static __device__ __forceinline__ double block_sum(double v, double* scratch, int tid) {
-#if !defined(LPC_SIMT_EMU)
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);   // 64-lane wavefront
-  const int wave = tid >> 6, lane = tid & 63;
-  if (lane == 0) scratch[wave] = v;
-  __syncthreads();
-  if (tid == 0)
-    for (int w = 1; w < NT / 64; ++w) v += scratch[w];
-#else
-  scratch[tid] = v;
-  __syncthreads();
-  if (tid == 0)
-    for (int w = 1; w < NT; ++w) v += scratch[w];
-#endif
-  return v;
-}
+#include "lpc_reduce_kernels.h"
 
 // (min, max - min) of item (b, d) over its C planes: the normalisation of recon.py:640-645
 // (amin / amax over (H, W, C); max(z - min) == max(z) - min because the subtraction is monotone)

@@ -54,8 +54,8 @@ static int m_admm_rows_fwd_x(Engine* e, const AdmmScalars* sc, const K1Rows* k1)
   if (k1) return fail("internal: half-length rows do not hold the TV / W half");
   return launch_k(e, LPC_K_ROW_FWD, k_rfwd_half_x<RNT, REM, RSK, RowPA>, dim3(2 * e->g.Hp, e->P), RNT, kRowSmem,
                   e->g, *sc,
-                  row_arg(e), (const real2*)e->planW.tw, (const real*)e->Rsp, (const real*)e->HVb[e->hcur],
-                  (const real*)e->HVb[e->hcur ^ 1], e->xi, (const real*)e->Y, e->S, spec_b(e));
+                  row_arg(e), (const real2*)e->planW.tw, (const real*)e->admm.Rsp, (const real*)e->admm.HVb[e->admm.hcur],
+                  (const real*)e->admm.HVb[e->admm.hcur ^ 1], e->admm.xi, (const real*)e->Y, e->S, spec_b(e));
 }
 #endif
 #else   // gradient-descent family
@@ -73,7 +73,7 @@ static int m_gd_rows_mid(Engine* e) {
   if constexpr (GdV2<RowP>::ok) {
     if (e->plan.gd_v2)     // second form (lpc_gd_v2_kernels.h): one-radix plan, M / R lanes per row
       return launch_k(e, LPC_K_ROW_INV, k_gd_resid_v2<GdV2<RowP>::NB, V2SK, RowPA>, dim3(g.H, e->P), GdV2<RowP>::NB, kV2Smem,
-                      geom_rev(e, e->plan.gd_rev_resid), row_arg(e), e->planW.tw, (const real2*)e->S, e->S2,
+                      geom_rev(e, e->plan.gd_rev_resid), row_arg(e), e->planW.tw, (const real2*)e->S, e->gd.S2,
                       (const real*)e->Y, make_fastdiv((unsigned)g.DC), make_fastdiv((unsigned)g.C));
   }
 #endif
@@ -89,7 +89,7 @@ static int m_gd_rows_update_fwd(Engine* e, const GdScalars* sc, const real* alph
     if (e->plan.gd_v2) {
       auto go = [&](auto kernel) {
         return launch_k(e, LPC_K_SPATIAL, kernel, dim3(g.H, e->P), GdV2<RowP>::NB, kV2Smem, geom_rev(e, e->plan.gd_rev_update),
-                        row_arg(e), e->planW.tw, (const real2*)e->S2, e->S, e->gx, e->gaux, alpha, *sc,
+                        row_arg(e), e->planW.tw, (const real2*)e->gd.S2, e->S, e->gd.gx, e->gd.gaux, alpha, *sc,
                         make_fastdiv((unsigned)g.C));
       };
       constexpr int NB = GdV2<RowP>::NB;
@@ -101,7 +101,7 @@ static int m_gd_rows_update_fwd(Engine* e, const GdScalars* sc, const real* alph
 #endif
   return launch_k(e, LPC_K_SPATIAL, k_rinv_gd_update_fwd_half<RNT, REM, RSK, RowPA>, dim3(g.H, e->P), RNT, kRowSmem,
                   geom_rev(e, e->plan.gd_rev_update),
-                  row_arg(e), e->planW.tw, (const real2*)e->S2, e->S, e->gx, e->gaux, alpha, *sc);
+                  row_arg(e), e->planW.tw, (const real2*)e->gd.S2, e->S, e->gd.gx, e->gd.gaux, alpha, *sc);
 }
 static int m_gd_bwd_head(Engine* e, const GdBwd* a) { return launch_gd_bwd_half<0, RNT, REM, RSK>(e, row_arg(e), *a); }
 static int m_gd_bwd_mid(Engine* e, const GdBwd* a) { return launch_gd_bwd_half<1, RNT, REM, RSK>(e, row_arg(e), *a); }
@@ -130,14 +130,14 @@ static int m_admm_rows_fwd_x(Engine* e, const AdmmScalars* sc, const K1Rows* k1)
     if constexpr (kK1Rows)
       return launch_k(e, LPC_K_ROW_FWD, k_rfwd_arrays_x<RNT, REM, RSK, RowPA, true, LPC_MOD_SLAY>, dim3(xrows, e->P), RNT, kRowSmem,
                       e->g, *sc,
-                      row_arg(e), (const real*)e->Rsp, (const real*)e->HVb[e->hcur], (const real*)e->HVb[e->hcur ^ 1],
-                      e->xi, (const real*)e->Y, SA, SB, *k1);
+                      row_arg(e), (const real*)e->admm.Rsp, (const real*)e->admm.HVb[e->admm.hcur], (const real*)e->admm.HVb[e->admm.hcur ^ 1],
+                      e->admm.xi, (const real*)e->Y, SA, SB, *k1);
     return fail("internal: this module's rows do not hold the TV / W half");
   }
   return launch_k(e, LPC_K_ROW_FWD, k_rfwd_arrays_x<RNT, REM, RSK, RowPA, false, LPC_MOD_SLAY>, dim3(xrows, e->P), RNT, kRowSmem,
                   e->g, *sc,
-                  row_arg(e), (const real*)e->Rsp, (const real*)e->HVb[e->hcur], (const real*)e->HVb[e->hcur ^ 1],
-                  e->xi, (const real*)e->Y, SA, SB, K1Rows{});
+                  row_arg(e), (const real*)e->admm.Rsp, (const real*)e->admm.HVb[e->admm.hcur], (const real*)e->admm.HVb[e->admm.hcur ^ 1],
+                  e->admm.xi, (const real*)e->Y, SA, SB, K1Rows{});
 }
 #endif
 #endif   // paired rows
@@ -164,8 +164,8 @@ static int m_admm_mid(Engine* e, const ColPass* cp, const AdmmScalars* sc, real 
   constexpr int PC = LPC_MOD_SLAY != 0 ? LPC_MOD_MID_PC : 0;      // precombined point-wise constants (k_mid_consts)
   return launch_k(e, LPC_K_COL_MID, k_cols_mid_admm_seq<NT, EM, MidPA, T, LPC_MOD_MID_MINW, LPC_MOD_MID_PRE != 0, LPC_MOD_SLAY, PC>,
                   dim3(cp->ntile_c * e->P), NT, (size_t)MidP::n * (T + 1) * sizeof(real2), e->g, pa, *cp, e->S, spec_b(e),
-                  PC ? (const real2*)e->midc : (const real2*)(LPC_MOD_SLAY ? e->Hs_t : e->Hs),
-                  PC ? (const real*)e->midrd : (const real*)(LPC_MOD_SLAY ? e->Gabs_t : e->Gabs), (const real2*)e->phr, (const real2*)e->phc, sc->mu1,
+                  PC ? (const real2*)e->admm.midc : (const real2*)(LPC_MOD_SLAY ? e->admm.Hs_t : e->Hs),
+                  PC ? (const real*)e->admm.midrd : (const real*)(LPC_MOD_SLAY ? e->admm.Gabs_t : e->admm.Gabs), (const real2*)e->phr, (const real2*)e->phc, sc->mu1,
                   sc->mu2, sc->mu3, inv_points(e->g), sb_outside_scale);
 #else                                   // both spectra side by side: [N][2 T]
   return launch_admm_mid<NT, EM, 2 * T, true, LPC_MOD_SLAY>(e, pa, *cp, *sc, sb_outside_scale);

@@ -8,7 +8,7 @@
 // (per-channel maxima, or the window mean and the energy for a PSF) and one pass that writes the float image;
 // the normalisers are derived on the device, so a capture goes camera buffer -> solver without touching the host.
 #pragma once
-#include "lpc_metric_kernels.h"
+#include "lpc_reduce_kernels.h"
 
 struct PrepGeom {
   int H, W, Cin, Cout;   // Cout = 1 when gray (or single_psf without channel repeat), else Cin

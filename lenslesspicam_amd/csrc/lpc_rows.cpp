@@ -36,7 +36,7 @@ int rows_inv_single(Engine* e, const real2* S, const RealDst& dst, int nplanes, 
   });
 }
 
-// ---- ADMM: rows of r_sp and a (e->Rsp, e->Aarr) -> the two work spectra --------------------------------------
+// ---- ADMM: rows of r_sp and a (e->admm.Rsp, e->admm.Aarr) -> the two work spectra --------------------------------------
 int admm_rows_fwd(Engine* e) {
   const PlaneGeom& g = e->g;
   if (e->mod && e->mod->admm_rows_fwd) return e->mod->admm_rows_fwd(e);

@@ -28,7 +28,7 @@ struct SPlan {
     for (int i = 0; i < st; ++i) v *= radix(i);
     return v;
   }
-  // same rule as plan_from_radices() in lpc_engine.cpp: the i + i/8 skew stays affine in every stage
+  // same rule as plan_from_radices() in lpc_setup.cpp: the i + i/8 skew stays affine in every stage
   static __host__ __device__ constexpr bool skew_ok() {
     for (int st = 0; st < nst; ++st) {
       if ((n / radix(st)) % 8 != 0) return false;

@@ -16,7 +16,7 @@ if [ "$1" = "--san" ]; then
 fi
 mkdir -p $B/o32 $B/o64 $B/modules
 CSRC=../../lenslesspicam_amd/csrc
-FP=$( (cat $CSRC/*.h $CSRC/*.cpp $CSRC/*.inc ../../include/lpc.h emu.cpp; echo "$SAN") | sha1sum | cut -c1-12)
+FP=$( (cat $CSRC/*.h $CSRC/*.cpp ../../include/lpc.h emu.cpp; echo "$SAN") | sha1sum | cut -c1-12)
 CXX="g++ -std=c++17 -O2 -fPIC $SAN -DLPC_SIMT_EMU -I$CSRC -I../../include -DLPC_SRC_FP=\"$FP\""
 CRC=$(python3 -c "import sys; sys.path.insert(0, '../..'); from lenslesspicam_amd import build; print('0x%08xu' % build.sources_crc())")
 CXX="$CXX -DLPC_SRC_CRC=$CRC"
@@ -26,16 +26,17 @@ if [ -n "$SAN" ]; then   # (a header, not -D: the value contains spaces)
   CXX="$CXX -include $B/san_defs.h"
 fi
 pids=""
+O32=""; O64=""        # the objects of the units that exist now (a kept $B may hold those of vanished ones)
 for f in $CSRC/*.cpp emu.cpp; do
   b=$(basename "$f" .cpp)
   [ "$b" = lpc_module ] && continue
+  O32="$O32 $B/o32/$b.o"; O64="$O64 $B/o64/$b.o"
   $CXX -c -x c++ "$f" -o $B/o32/$b.o & pids="$pids $!"
   [ -z "$SAN" ] && { $CXX -DLPC_DOUBLE -c -x c++ "$f" -o $B/o64/$b.o & pids="$pids $!"; }     # (--san: float32 only)
 done
 for p in $pids; do wait $p; done
-rm -f $B/o32/lpc_module.o $B/o64/lpc_module.o $B/o32/lpc_gd_update_fwd.o $B/o64/lpc_gd_update_fwd.o
-g++ -shared $SAN -Wl,-soname,liblpc_emu.so $B/o32/*.o -o $B/liblpc_emu.so -lpthread -ldl
-[ -z "$SAN" ] && g++ -shared -Wl,-soname,liblpc_emu_f64.so $B/o64/*.o -o $B/liblpc_emu_f64.so -lpthread -ldl
+g++ -shared $SAN -Wl,-soname,liblpc_emu.so $O32 -o $B/liblpc_emu.so -lpthread -ldl
+[ -z "$SAN" ] && g++ -shared -Wl,-soname,liblpc_emu_f64.so $O64 -o $B/liblpc_emu_f64.so -lpthread -ldl
 # modules built from other sources are dead weight
 find $B/modules -name 'lpcmod_*.so' ! -name "lpcmod_emu_${FP}_*" -delete 2>/dev/null || true
 test -f $B/liblpc_emu.so && { [ -n "$SAN" ] || test -f $B/liblpc_emu_f64.so; }

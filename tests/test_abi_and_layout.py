@@ -38,6 +38,51 @@ def test_emulator_build_exports_the_same_abi(emu_lib):
     assert "emu" in emu_lib.backend()
 
 
+def test_workspace_bytes_moves_by_what_was_allocated_or_released(emu_lib):
+    """lpc_workspace_bytes after create, after schedules of n and 2n, and after lpc_fista_record 1 / -1 / 0: every step
+    changes it by exactly the bytes of what the step allocated or released, worked out here from the handle's shape
+    (include/lpc.h: lpc_set_fista_schedule, lpc_fista_record).  No absolute value is asserted."""
+    for lib in [emu_lib] + ([emu_lib.f64] if emu_lib.f64 else []):     # (the sanitizer flavour is float32 only)
+        _workspace_bytes_steps(lib)
+
+
+def _workspace_bytes_steps(lib):
+    from lenslesspicam_amd import _native
+
+    H, W, C, B, n, real = 10, 12, 3, 2, 3, 8 if lib.real == "float64" else 4
+    h = lib.create(algo=_native.ALGO_FISTA, height=H, width=W, channels=C, batch=B)
+    created = h.workspace_bytes()
+
+    def schedule(k):
+        h.set_fista_schedule([[1e-3] * C] * k, [0.1] * k, 0)
+        return h.workspace_bytes()
+
+    def record(on):
+        h.fista_record(on)
+        return h.workspace_bytes()
+
+    def tape(k):     # (2k + 4) un-padded state arrays + k * P * H * 2 doubles of per-row partial sums, P = B * C planes
+        return (2 * k + 4) * B * C * H * W * real + k * B * C * H * 2 * 8
+
+    assert record(1) == created                       # no schedule yet: nothing to size a tape by
+    assert record(0) == created
+    assert schedule(n) == created + n * C * real      # the table alpha[n][C]
+    assert schedule(n) == created + n * C * real      # ... which a schedule that fits re-uses
+    assert schedule(2 * n) == created + 2 * n * C * real      # grown: the old table is given back
+    assert schedule(n) == created + 2 * n * C * real          # a shorter one fits the grown table
+    base = h.workspace_bytes()
+    assert record(1) == base + tape(n)
+    assert record(1) == base + tape(n)                # twice in a row: the same tape
+    assert record(-1) == base + tape(n)               # pause: the tape stays allocated
+    assert record(1) == base + tape(n)
+    assert record(0) == base                          # release
+    assert record(-1) == base
+    assert record(1) == base + tape(n) and record(0) == base      # a full cycle returns to where it started
+    schedule(0)
+    assert record(1) == base and record(0) == base    # schedule cleared (its table stays): nothing to size a tape by
+    h.close()
+
+
 def test_norm_enumerators_match_the_binding_and_the_reference_strings():
     """enum lpc_norm (include/lpc.h) <-> _native.NORM <-> the three strings rfft_convolve.py:27,121 hands to rfft2"""
     from lenslesspicam_amd import _native
