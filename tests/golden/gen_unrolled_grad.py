@@ -17,6 +17,8 @@ compared without exclusions: an element that takes the other branch in float32 m
 than 1e-5 of its own scale, and the reference's own float32 run, the tests' yardstick, contains the same effect.
 Its big arrays are stored as longrun_inputs.samples() crops + lattice of the float64 run; of the float32 run only the
 distances to the float64 run over the WHOLE arrays are kept (``rel32_*``).
+The small cases (non-negative PSF, measurement in [0, 1)) clamp under 1 % of the elements in every projection; the
+coverage of ACTIVE masks lives in tests/test_unrolled_grad_sweep.py (signed measurement, torch.autograd as reference).
 """
 import os
 import sys
