@@ -207,6 +207,20 @@ int lpc_fista_backward(lpc_handle h, const lpc_real* dev_grad_out,   /* (B,D,H,W
                        lpc_real* dev_grad_coef,    /* n,   gradient w.r.t. coef[]                               */
                        lpc_real* dev_grad_init,    /* (B,D,H,W,C) or NULL: w.r.t. the initial estimate          */
                        void* stream);
+/* lpc_fista_backward_psf: lpc_fista_backward plus the gradient w.r.t. the PSF given to lpc_set_psf, summed over the batch
+ * (the start value and the schedule count as constants, as in the reference's forward(batch, psfs=...)).  With the
+ * tape's y_i, the sweep's gz_i and Hg_i = Cv(gz_i), the residual r_i = Cv(y_i) - b recomputed, P = zero-padding,
+ * F = rfft2, K = crop . ifftshift . irfft2 and s the norm factor of the PSF spectrum, iteration i adds
+ *   -alpha[i][c] * s * sum over the batch of  K(conj(F(P gz_i)) . F(P r_i)) + K(conj(F(P y_i)) . F(P Hg_i)).
+ * Same refusals (and messages) as lpc_fista_backward; deterministic (no atomics).  Its workspace is allocated at the first
+ * call, counted in lpc_workspace_bytes, kept across a pause and freed with the tape by lpc_fista_record(h, 0):
+ *   3 * P * Hp * cpitch * 2 * sizeof(lpc_real)  +  P * H * W * sizeof(lpc_real)      bytes,
+ * P = B * C planes, cpitch = Wp / 2 + 1 rounded up to a multiple of 16 (Hp, Wp: lpc_padded_shape).  lpc_fista_backward
+ * itself allocates and launches nothing of this.  dev_grad_psf NULL: lpc_fista_backward. */
+int lpc_fista_backward_psf(lpc_handle h, const lpc_real* dev_grad_out, lpc_real* dev_grad_data, lpc_real* dev_grad_alpha,
+                           lpc_real* dev_grad_coef, lpc_real* dev_grad_init,
+                           lpc_real* dev_grad_psf,    /* (D,H,W,C): w.r.t. the PSF                               */
+                           void* stream);
 
 /* ---- the hot loop: `for i in range(n_iter): self._update(i)`  recon.py:575-576 ------ */
 /* exactly n_iter iterations, asynchronous on `stream`; no early exit exists on this path */

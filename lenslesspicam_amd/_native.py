@@ -129,6 +129,7 @@ class Lib:
             "lpc_set_fista_schedule": [vp, C.c_int, vp, vp, vp],
             "lpc_fista_record": [vp, C.c_int],
             "lpc_fista_backward": [vp, fp, fp, fp, fp, fp, vp],
+            "lpc_fista_backward_psf": [vp, fp, fp, fp, fp, fp, fp, vp],
             "lpc_form_image": [vp, fp, vp],
             "lpc_get_state": [vp, C.c_char_p, fp, vp],
             "lpc_profile_enable": [vp, C.c_int],
@@ -277,6 +278,13 @@ class Handle:
         """reverse sweep over the tape: device pointers; ``grad_data_ptr`` / ``grad_init_ptr`` may be None"""
         self._c(self.lib.dll.lpc_fista_backward(self.h, grad_out_ptr, grad_data_ptr, grad_alpha_ptr, grad_coef_ptr,
                                                 grad_init_ptr, stream))
+
+    def fista_backward_psf(self, grad_out_ptr, grad_data_ptr, grad_alpha_ptr, grad_coef_ptr, grad_init_ptr, grad_psf_ptr,
+                           stream=0):
+        """``fista_backward`` plus the gradient w.r.t. the PSF, (D, H, W, C), summed over the batch
+        (lpc_fista_backward_psf)"""
+        self._c(self.lib.dll.lpc_fista_backward_psf(self.h, grad_out_ptr, grad_data_ptr, grad_alpha_ptr, grad_coef_ptr,
+                                                    grad_init_ptr, grad_psf_ptr, stream))
 
     def clear_admm_schedule(self):
         self._c(self.lib.dll.lpc_set_admm_schedule(self.h, 0, None, None, None, None))

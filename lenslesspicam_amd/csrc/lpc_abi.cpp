@@ -210,8 +210,8 @@ int lpc_fista_record(lpc_handle e, int on) {
   return e->fista.sched_n > 0 ? gd_tape_alloc(e) : 0;     // (no schedule yet: lpc_reset allocates)
 }
 
-int lpc_fista_backward(lpc_handle e, const real* dev_grad_out, real* dev_grad_data, real* dev_grad_alpha,
-                       real* dev_grad_coef, real* dev_grad_init, void* stream) {
+static int fista_backward(lpc_handle e, const real* dev_grad_out, real* dev_grad_data, real* dev_grad_alpha,
+                          real* dev_grad_coef, real* dev_grad_init, real* dev_grad_psf, void* stream) {
   if (!e || !dev_grad_out || !dev_grad_alpha || !dev_grad_coef) return fail("lpc_fista_backward: null argument");
   if (e->cfg.algo != LPC_ALGO_FISTA) return fail("lpc_fista_backward: not a FISTA handle");
   if (e->fista.sched_n <= 0) return fail("lpc_fista_backward: the handle has no schedule (lpc_set_fista_schedule)");
@@ -229,7 +229,16 @@ int lpc_fista_backward(lpc_handle e, const real* dev_grad_out, real* dev_grad_da
     if (a == (real)0.) return fail("lpc_fista_backward: a step alpha of the schedule is 0");
   if (dev_grad_data && !e->data_set) return fail("lpc_fista_backward: no data set");
   e->stream = (lpcStream_t)stream;
-  return gd_backward(e, dev_grad_out, dev_grad_data, dev_grad_alpha, dev_grad_coef, dev_grad_init);
+  return gd_backward(e, dev_grad_out, dev_grad_data, dev_grad_alpha, dev_grad_coef, dev_grad_init, dev_grad_psf);
+}
+int lpc_fista_backward(lpc_handle e, const real* dev_grad_out, real* dev_grad_data, real* dev_grad_alpha,
+                       real* dev_grad_coef, real* dev_grad_init, void* stream) {
+  return fista_backward(e, dev_grad_out, dev_grad_data, dev_grad_alpha, dev_grad_coef, dev_grad_init, nullptr, stream);
+}
+// ... and the gradient w.r.t. the PSF (dev_grad_psf null: lpc_fista_backward); same refusals, same messages
+int lpc_fista_backward_psf(lpc_handle e, const real* dev_grad_out, real* dev_grad_data, real* dev_grad_alpha,
+                           real* dev_grad_coef, real* dev_grad_init, real* dev_grad_psf, void* stream) {
+  return fista_backward(e, dev_grad_out, dev_grad_data, dev_grad_alpha, dev_grad_coef, dev_grad_init, dev_grad_psf, stream);
 }
 
 int lpc_iterate(lpc_handle e, int n_iter, void* stream) {

@@ -35,8 +35,10 @@ int cols_passB_fwd(Engine* e, real2* S, int nplanes, int zr0, int zr1) {
 
 // middle of a convolution on S (nplanes): [A] -> B fwd * H * B inv -> [A inv]
 int conv_middle(Engine* e, real2* S, int nplanes, bool adjoint, int zr0, int zr1,
-                       bool crop_rows_only) {
+                       bool crop_rows_only, const real2* mult, int mult_planes) {
   const PlaneGeom& g = e->g;
+  const real2* Hs = mult ? mult : e->Hs;
+  const int hplanes = mult ? mult_planes : e->Ppsf;
   const bool split = e->plan.N1 > 1;
   if (split) LPC_OK(cols_passA(e, S, nplanes, false, zr0, zr1, LPC_K_COL_A_FWD));
   ColPass cp = e->passB;
@@ -48,7 +50,7 @@ int conv_middle(Engine* e, real2* S, int nplanes, bool adjoint, int zr0, int zr1
   auto reg_mid = [&](auto kernel) {
     const dim3 rgrid((g.Wc + 63) / 64, cp.G, nplanes);
     return launch_k(e, LPC_K_COL_MID, kernel, rgrid, 64, 0, geom_rev(e, e->plan.gd_rev_mid), e->planB, cp, S,
-                    (const real2*)e->Hs, adjoint ? 1 : 0, hscale, e->Ppsf);
+                    Hs, adjoint ? 1 : 0, hscale, hplanes);
   };
   const int regN = e->plan.conv_mid_reg;
   if (regN == 48) { LPC_OK(reg_mid(k_cols_mid_mul_reg<8, 6>)); }
@@ -61,7 +63,7 @@ int conv_middle(Engine* e, real2* S, int nplanes, bool adjoint, int zr0, int zr1
   LPC_OK(dispatch_cfg(cp.N * cp.T, [&](auto NT, auto EM) {
     constexpr int nt = decltype(NT)::value, em = decltype(EM)::value;
     return launch_k(e, LPC_K_COL_MID, k_cols_mid_mul<nt, em>, grid, nt, (size_t)cp.N * cp.T * sizeof(real2), g,
-                    e->planB, cp, S, (const real2*)e->Hs, adjoint ? 1 : 0, hscale, e->Ppsf);
+                    e->planB, cp, S, Hs, adjoint ? 1 : 0, hscale, hplanes);
   }));
   if (split) LPC_OK(cols_passA(e, S, nplanes, true, 0, g.Hp, LPC_K_COL_A_INV, crop_rows_only));
   return 0;

@@ -188,6 +188,11 @@ struct FistaSchedule {
   real* tape = nullptr;
   double* tape_part = nullptr;
   int tape_n = 0;              // iterations the tape was allocated for
+  // PSF gradient (lpc_fista_backward_psf), allocated at its first call and freed with the tape: three spectrum buffers of P
+  // planes (residual rows / cross term; full spectrum of P gz_i / rows of P Hg_i; full spectrum of P y_i) and the
+  // accumulator, P un-padded planes
+  real2* psf_spec = nullptr;
+  real* psf_acc = nullptr;
   long tape_iters = -1;        // iterations recorded since the last reset (-1: nothing recorded)
 };
 
@@ -329,12 +334,13 @@ struct LpcModule {
   int (*admm_rows_fwd)(Engine*);
   int (*admm_rows_fwd_x)(Engine*, const AdmmScalars*, const K1Rows* k1);   // k1: + the TV / W half (k1_rows)
   int (*admm_rows_inv)(Engine*, real* Vout, real* HVout, int skip_hv_outside);
-  int (*gd_rows_mid)(Engine*);
+  int (*gd_rows_mid)(Engine*, const real2* Sin, real2* Sout);
   int (*gd_rows_update)(Engine*, const GdScalars*, const real* alpha);
   int (*gd_rows_update_fwd)(Engine*, const GdScalars*, const real* alpha);
   int (*gd_bwd_head)(Engine*, const GdBwd*);       // reverse mode of unrolled FISTA (lpc_gd_bwd_kernels.h), half rows
   int (*gd_bwd_mid)(Engine*, const GdBwd*);
   int (*gd_bwd_update)(Engine*, const GdBwd*);
+  int (*gd_bwd_acc)(Engine*, const GdBwd*, const real2* Sin);   // ... the PSF gradient's accumulate (MODE 3)
   int (*cols_passA)(Engine*, const ColPass*, real2* S, int nplanes, int inverse, int kid);
   int (*admm_mid)(Engine*, const ColPass*, const AdmmScalars*, real sb_outside_scale);
   int k1_rows;    // admm_rows_fwd_x takes the TV / W half of the image-domain work as well (k_rfwd_arrays_x<.., K1>)
@@ -367,6 +373,7 @@ int setup_geometry(Engine* e);
 int alloc_common(Engine* e);                                    // PSF spectrum, work spectra, data / staging planes
 int set_psf(Engine* e, const real* dev_psf);
 int fft2_forward_setup(Engine* e, const RealSrc& src, real2* S, int nplanes);
+int cols_fwd_full(Engine* e, real2* S, int nplanes, int zr0, int zr1);   // row spectra (rows [zr0, zr1)) -> full 2-D spectra, Hs layout
 int convolve_planar(Engine* e, const real* xin, real* xout, int nplanes, bool padded_io, bool adjoint);
 int convolve_hwc(Engine* e, const real* dev_x, real* dev_out, int n, int x_channels, bool adjoint, bool spectrum);
 int hwc_to_planar(Engine* e, const real* src, real* dst, int nimg, int rows, int cols, int pitch, long dplane,
@@ -400,7 +407,8 @@ int gd_set_schedule(Engine* e, int n, const real* alpha, const real* coef);
 int gd_reset(Engine* e);
 int gd_iterate(Engine* e, int n_iter, int split = 0);
 int gd_finish_split(Engine* e, const real* dev_projected);
-int gd_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_alpha, real* grad_coef, real* grad_init);
+int gd_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_alpha, real* grad_coef, real* grad_init,
+                real* grad_psf = nullptr);
 int gd_form_image(Engine* e, real* dev_out);
 int gd_get_state(Engine* e, const std::string& nm, real* dev_out);
 int gd_kernel_bytes(Engine* e, int kid, double* bytes);
@@ -414,12 +422,15 @@ int admm_rows_inv(Engine* e, real* Vout, real* HVout, bool skip_hv_outside = fal
 int cols_passA(Engine* e, real2* S, int nplanes, bool inverse, int zr0, int zr1, int kid, bool crop_rows_only = false,
                real sb_outside_scale = (real)0.);
 int cols_passB_fwd(Engine* e, real2* S, int nplanes, int zr0, int zr1);
-int conv_middle(Engine* e, real2* S, int nplanes, bool adjoint, int zr0, int zr1, bool crop_rows_only = false);
+// mult (mult_planes planes, Hs layout): the multiplier spectrum in place of the PSF's; plane p reads plane p % mult_planes
+int conv_middle(Engine* e, real2* S, int nplanes, bool adjoint, int zr0, int zr1, bool crop_rows_only = false,
+                const real2* mult = nullptr, int mult_planes = 0);
 int admm_cols(Engine* e, const AdmmScalars& sc);   // sc.skipa: forward pass A rescales the kept rows of SB                // [pass A] -> fused ADMM middle -> [inverse pass A]
 // lpc_gd.cpp, lpc_gd_update.cpp (one kernel family each)
-int gd_rows_mid(Engine* e);                                     // irfft rows -> residual -> rfft rows (S -> S2)
+int gd_rows_mid(Engine* e, const real2* Sin, real2* Sout);      // irfft rows -> residual -> rfft rows (the iteration: S -> S2)
 int gd_rows_update(Engine* e, const GdScalars& sc, const real* alpha);   // irfft rows -> fused projected update
 // lpc_gd_bwd.cpp
-int gd_bwd_rows(Engine* e, int mode, const GdBwd& a);           // reverse-mode rows: 0 head, 1 middle, 2 update + next head
+int gd_bwd_rows(Engine* e, int mode, const GdBwd& a, const real2* Sin = nullptr);   // reverse-mode rows: 0 head, 1 middle, 2 update + next head, 3 PSF-gradient accumulate (rows of Sin)
+int gd_bwd_psf_sum(Engine* e, const real* acc, real* grad_psf); // ... and its sum over the batch -> (1, H, W, C)
 
 #include "lpc_launch.h"

@@ -15,6 +15,9 @@
 //   MODE 1   rows (S) -> irfft -> shift + crop = Hg -> g_b -> re-pad              -> rfft rows (S2)
 //   MODE 2   rows (S2) -> irfft -> shift + crop = D(Hg) -> gy -> head of i-1      -> rfft rows (S);
 //            for i = 0 the tail instead: g_init = gy + carry, no transform
+//   MODE 3   rows (any spectrum buffer) -> irfft -> shift + crop = v -> acc (+)= -a_i s v, no transform afterwards:
+//            the PSF gradient's accumulate (lpc_fista_backward_psf).  Per iteration the sweep hands it two cross terms,
+//            v = K(conj(F(P gz_i)) . F(P r_i)) and v = K(conj(F(P y_i)) . F(P Hg_i)); k_gd_bwd_gpsf sums acc over the batch
 // The sums are deterministic: every workgroup (one image row, or one row pair) leaves its two partial sums, accumulated in
 // double, in a scratch array; k_gd_bwd_finish adds them up in a fixed order.  No atomics.
 #pragma once
@@ -24,27 +27,28 @@ struct GdBwd {
   const real* alpha;   // [C] a_i of the iteration whose rows pass through (MODE 1, 2)
   real* gz;            // [P][H][W] work: gy in (MODE 0: dL/dout, planar) / gz out; MODE 2 reads gz back; tail: g_init out
   real* carry;         // [P][H][W] work
-  real* gb;            // [P][H][W] MODE 1: a_i Hg summed over the iterations, or null (no data gradient asked for)
+  real* gb;            // [P][H][W] MODE 1: a_i Hg summed over the iterations, or null (no data gradient asked for);
+                       // MODE 3: the PSF gradient's accumulator
   const real* xk;      // the head's iteration j: tape slots xk_j, xk_{j-1} (j = 0: y_0) and y_j
   const real* xkp;
   const real* y;
   const real* yn;      // MODE 0: y_n
   double* part;        // the head's partial sums: [P][gridDim.x][2] = (g_c, g_a) terms
-  real coef;           // c_j
-  int gb_first;        // MODE 1 of iteration n-1: gb is written, not added to
+  real coef;           // c_j; MODE 3: -s, the PSF spectrum's norm factor negated
+  int gb_first;        // MODE 1 of iteration n-1 (MODE 3: the first term of the sweep): gb is written, not added to
   int tail;            // MODE 2 of iteration 0
 };
 
 struct GdBwdIn { real v, gz, carry, xk, xkp, y, yn, gb; };
 struct GdBwdOut { real ret, gz, carry, gb; };
 
-// one element: `in.v` is the sample the inverse transform produced for it (MODE 1: Hg, MODE 2: D(Hg)); returns what the
-// forward transform takes (out.ret) and what goes back to memory
+// one element: `in.v` is the sample the inverse transform produced for it (MODE 1: Hg, MODE 2: D(Hg), MODE 3: a cross
+// term); returns what the forward transform takes (out.ret) and what goes back to memory.  `al`: a_i (MODE 3: -s a_i)
 template <int MODE>
 static __device__ __forceinline__ GdBwdOut gd_bwd_val(const GdBwdIn& in, const GdBwd& a, real al, double& sc, double& sa) {
   GdBwdOut o;
   o.ret = o.gz = o.carry = o.gb = (real)0.;
-  if (MODE == 1) {
+  if (MODE == 1 || MODE == 3) {
     const real t = al * in.v;
     o.gb = a.gb_first ? t : in.gb + t;
     o.ret = in.v;
@@ -72,7 +76,7 @@ static __device__ __forceinline__ real gd_bwd_one(const GdBwd& a, long o, real v
   GdBwdIn in;
   in.v = v;
   in.gz = in.carry = in.xk = in.xkp = in.y = in.yn = in.gb = (real)0.;
-  if (MODE == 1) {
+  if (MODE == 1 || MODE == 3) {
     if (!a.gb) return v;
     if (!a.gb_first) in.gb = a.gb[o];
   } else {
@@ -82,7 +86,7 @@ static __device__ __forceinline__ real gd_bwd_one(const GdBwd& a, long o, real v
     if (MODE == 0 || !a.tail) { in.xk = a.xk[o]; in.xkp = a.xkp[o]; in.y = a.y[o]; }
   }
   const GdBwdOut r = gd_bwd_val<MODE>(in, a, al, sc, sa);
-  if (MODE == 1) {
+  if (MODE == 1 || MODE == 3) {
     a.gb[o] = r.gb;
   } else {
     a.gz[o] = r.gz;
@@ -96,7 +100,7 @@ template <int MODE>
 static __device__ __forceinline__ real2 gd_bwd_pair(const GdBwd& a, long o, real2 v, real al, double& sc, double& sa) {
   const real2 z2 = make_real2((real)0., (real)0.);
   real2 gz = z2, carry = z2, xk = z2, xkp = z2, y = z2, yn = z2, gb = z2;
-  if (MODE == 1) {
+  if (MODE == 1 || MODE == 3) {
     if (!a.gb) return v;
     if (!a.gb_first) gb = *(const real2*)(a.gb + o);
   } else {
@@ -111,7 +115,7 @@ static __device__ __forceinline__ real2 gd_bwd_pair(const GdBwd& a, long o, real
   i0.v = v.x; i0.gz = gz.x; i0.carry = carry.x; i0.xk = xk.x; i0.xkp = xkp.x; i0.y = y.x; i0.yn = yn.x; i0.gb = gb.x;
   i1.v = v.y; i1.gz = gz.y; i1.carry = carry.y; i1.xk = xk.y; i1.xkp = xkp.y; i1.y = y.y; i1.yn = yn.y; i1.gb = gb.y;
   const GdBwdOut r0 = gd_bwd_val<MODE>(i0, a, al, sc, sa), r1 = gd_bwd_val<MODE>(i1, a, al, sc, sa);
-  if (MODE == 1) {
+  if (MODE == 1 || MODE == 3) {
     *(real2*)(a.gb + o) = make_real2(r0.gb, r1.gb);
   } else {
     *(real2*)(a.gz + o) = make_real2(r0.gz, r1.gz);
@@ -171,7 +175,7 @@ __global__ __launch_bounds__(NT) void k_gd_bwd_half(PlaneGeom g, PL plan, const 
   }
   // slot j now holds samples (2j, 2j+1) of the convolution before the shift; padded sample m of the NEW row =
   // (m in window) ? element [m - sw], which takes convolution sample (m + Wp/2) mod Wp : 0
-  const real al = MODE != 0 ? a.alpha[pl % g.C] : (real)0.;
+  const real al = MODE == 3 ? a.coef * a.alpha[pl % g.C] : MODE != 0 ? a.alpha[pl % g.C] : (real)0.;
   const long base = pl * g.uplane + (long)u * g.W;
   const bool pair = ((g.sw | g.W | hw) & 1) == 0;
   double sc = 0., sa = 0.;
@@ -196,7 +200,7 @@ __global__ __launch_bounds__(NT) void k_gd_bwd_half(PlaneGeom g, PL plan, const 
     }
     return make_real2(sample(2 * i), sample(2 * i + 1));
   };
-  if (MODE == 2 && a.tail) {     // g_init: the elements of the row, nothing to transform
+  if (MODE == 3 || (MODE == 2 && a.tail)) {     // acc / g_init: the elements of the row, nothing to transform
     for (int i = tid; i < M; i += NT) (void)newrow(i, 0);
     return;
   }
@@ -232,7 +236,7 @@ __global__ __launch_bounds__(NT) void k_gd_bwd_paired(PlaneGeom g, Fft1dPlan pla
     __syncthreads();
     fft_tile<NT, EMAX, true, SK, true>(s, plan, 1, make_fastdiv_dev1(), tid, LdsNatural{}, LdsNatural{}, NoFix{}, 0, 0);
   }
-  const real al = MODE != 0 ? a.alpha[pl % g.C] : (real)0.;
+  const real al = MODE == 3 ? a.coef * a.alpha[pl % g.C] : MODE != 0 ? a.alpha[pl % g.C] : (real)0.;
   const long base = pl * g.uplane + (long)u0 * g.W;
   double sc = 0., sa = 0.;
   auto newrow = [&](int i, int) {
@@ -245,7 +249,7 @@ __global__ __launch_bounds__(NT) void k_gd_bwd_paired(PlaneGeom g, Fft1dPlan pla
     r.y = v1 ? gd_bwd_one<MODE>(a, base + g.W + c, z.y, al, sc, sa) : (real)0.;
     return r;
   };
-  if (MODE == 2 && a.tail) {
+  if (MODE == 3 || (MODE == 2 && a.tail)) {
     for (int i = tid; i < g.Wp; i += NT) (void)newrow(i, 0);
     return;
   }
@@ -301,5 +305,19 @@ __global__ __launch_bounds__(NT) void k_gd_bwd_gdata(const real* LPC_RESTRICT gb
       for (int c = 1; c < C; ++c) sum += p[(long)c * uplane];
       out[img * uplane + e] = sum;
     }
+  }
+}
+
+// planar (P = B*C planes) PSF-gradient accumulator -> (1, H, W, C), the PSF's layout: the sum over the batch in the order
+// of the frames
+template <int NT>
+__global__ __launch_bounds__(NT) void k_gd_bwd_gpsf(const real* LPC_RESTRICT acc, real* LPC_RESTRICT out, long uplane,
+                                                     int C, int B) {
+  const int c = blockIdx.y;
+  for (long e = (long)blockIdx.x * NT + threadIdx.x; e < uplane; e += (long)gridDim.x * NT) {
+    const real* p = acc + (long)c * uplane + e;
+    real sum = p[0];
+    for (int b = 1; b < B; ++b) sum += p[(long)b * C * uplane];
+    out[e * C + c] = sum;
   }
 }

@@ -61,10 +61,25 @@ int gd_set_schedule(Engine* e, int n, const real* alpha, const real* coef) {
 }
 void gd_tape_free(Engine* e) {
   FistaSchedule& f = e->fista;
+  dev_free(e, f.psf_spec);       // the PSF gradient's workspace goes with the tape
+  dev_free(e, f.psf_acc);
+  f.psf_spec = nullptr; f.psf_acc = nullptr;
   if (!f.tape) return;
   dev_free(e, f.tape);
   dev_free(e, f.tape_part);
   f.tape = nullptr; f.tape_part = nullptr; f.tape_n = 0; f.tape_iters = -1;
+}
+// workspace of the PSF gradient (FistaSchedule::psf_spec, psf_acc; include/lpc.h: lpc_fista_backward_psf), on first use
+static int gd_psf_ws_alloc(Engine* e) {
+  FistaSchedule& f = e->fista;
+  if (f.psf_spec) return 0;
+  LPC_OK(dev_alloc(e, &f.psf_spec, (size_t)3 * e->g.cplane * e->P));
+  if (dev_alloc(e, &f.psf_acc, (size_t)e->g.uplane * e->P)) {      // all or nothing
+    dev_free(e, f.psf_spec);
+    f.psf_spec = nullptr;
+    return 1;
+  }
+  return 0;
 }
 int gd_tape_alloc(Engine* e) {
   FistaSchedule& f = e->fista;
@@ -124,7 +139,7 @@ int gd_iterate(Engine* e, int n_iter, int split) {
     e->gd.fwd_done = false;
     LPC_OK(conv_middle(e, e->S, e->P, false, g.sh, g.sh + g.H, true));
     // (H x - y), straight back into the frequency domain
-    LPC_OK(gd_rows_mid(e));
+    LPC_OK(gd_rows_mid(e, e->S, e->gd.S2));
     // H^T (.)
     LPC_OK(conv_middle(e, e->gd.S2, e->P, true, g.sh, g.sh + g.H, true));
     GdScalars sc;
@@ -164,9 +179,16 @@ int gd_iterate(Engine* e, int n_iter, int split) {
   return 0;
 }
 
-// reverse sweep over the tape (lpc_fista_backward; lpc_gd_bwd_kernels.h): per iteration the forward's five launches
+// reverse sweep over the tape (lpc_fista_backward; lpc_gd_bwd_kernels.h): per iteration the forward's five launches.
+// grad_psf (lpc_fista_backward_psf) adds, per iteration i, with r_i = Cv(y_i) - b recomputed from the tape:
+//   g_psf += -a_i s sum over the batch of  K(conj(F(P gz_i)) . F(P r_i)) + K(conj(F(P y_i)) . F(P Hg_i))
+// (the gradient through D, and through Cv: a convolution is symmetric in its two arguments, so the derivative w.r.t. the
+// PSF is the adjoint convolution whose "PSF" is the other argument).  Launches: forward rows of y_i, its copy's column
+// passes (-> F(P y_i)), the forward's middle + residual rows (-> rows of P r_i), the column passes of a copy of the head's
+// rows (-> F(P gz_i)), the middle with F(P gz_i) as the multiplier + accumulate rows, and after MODE 1 the middle on a
+// copy of the rows of P Hg_i with F(P y_i) as the multiplier + accumulate rows.  Without grad_psf nothing changes.
 int gd_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_alpha, real* grad_coef,
-                       real* grad_init) {
+                       real* grad_init, real* grad_psf) {
   const PlaneGeom& g = e->g;
   const int n = e->fista.tape_n, C = e->cfg.channels;
   const int rows = e->mod && e->mod->gd_bwd_head ? g.H : (e->plan.rows_half ? g.H : (g.H + 1) / 2);   // workgroups per plane
@@ -181,14 +203,50 @@ int gd_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_alp
     a.coef = e->fista.coef[(size_t)j];
     a.part = e->fista.tape_part + (long)j * pstride;
   };
+  // PSF gradient: spectrum buffers W0 (rows of y_i -> Cv(y_i); then F(P gz_i); then the rows of P Hg_i -> second cross
+  // term), W1 (rows of P r_i -> first cross term), W2 (F(P y_i))
+  const size_t sbytes = (size_t)g.cplane * e->P * sizeof(real2);
+  real2 *W0 = nullptr, *W1 = nullptr, *W2 = nullptr;
+  GdBwd pa{};          // the accumulate's arguments (MODE 3)
+  if (grad_psf) {
+    LPC_OK(gd_psf_ws_alloc(e));
+    W0 = e->fista.psf_spec; W1 = W0 + (size_t)g.cplane * e->P; W2 = W1 + (size_t)g.cplane * e->P;
+    double s = 1.0;      // set_psf: the norm factor of the PSF spectrum
+    if (e->cfg.norm == LPC_NORM_ORTHO) s = 1.0 / std::sqrt((double)g.Hp * (double)g.Wp);
+    if (e->cfg.norm == LPC_NORM_FORWARD) s = 1.0 / ((double)g.Hp * (double)g.Wp);
+    pa.gb = e->fista.psf_acc;
+    pa.coef = (real)-s;
+    pa.gb_first = 1;
+  }
+  auto psf_term = [&](real2* Srows, const real2* mult) {      // K(conj(mult) . column transform of Srows) -> acc
+    LPC_OK(conv_middle(e, Srows, e->P, true, g.sh, g.sh + g.H, true, mult, e->P));
+    LPC_OK(gd_bwd_rows(e, 3, pa, Srows));
+    pa.gb_first = 0;
+    return 0;
+  };
   LPC_OK(hwc_to_planar(e, grad_out, a.gz, e->cfg.batch, g.H, g.W, g.W, g.uplane));
   head_of(n - 1);
   LPC_OK(gd_bwd_rows(e, 0, a));
   for (int i = n - 1; i >= 0; --i) {
     a.alpha = e->fista.galpha_sched + (long)i * C;
+    if (grad_psf) {
+      pa.alpha = a.alpha;
+      LPC_OK(rows_fwd_single(e, src_unpadded(e, tape_y(e, i)), W0, e->P, LPC_K_ROW_FWD));
+      LPC_OK(rows_fwd_single(e, src_unpadded(e, tape_y(e, i)), W2, e->P, LPC_K_ROW_FWD));   // (cheaper than a copy of W0)
+      LPC_OK(cols_fwd_full(e, W2, e->P, g.sh, g.sh + g.H));                     // F(P y_i)
+      LPC_OK(conv_middle(e, W0, e->P, false, g.sh, g.sh + g.H, true));         // Cv(y_i)
+      LPC_OK(gd_rows_mid(e, W0, W1));                                           // rows of P r_i
+      LPC_RT(rt::copy_d2d_async(W0, e->S, sbytes, e->stream));
+      LPC_OK(cols_fwd_full(e, W0, e->P, g.sh, g.sh + g.H));                     // F(P gz_i)
+      LPC_OK(psf_term(W1, W0));
+    }
     LPC_OK(conv_middle(e, e->S, e->P, false, g.sh, g.sh + g.H, true));       // Cv(gz)
     a.gb_first = i == n - 1 ? 1 : 0;
     LPC_OK(gd_bwd_rows(e, 1, a));
+    if (grad_psf) {
+      LPC_RT(rt::copy_d2d_async(W0, e->gd.S2, sbytes, e->stream));             // rows of P Hg_i
+      LPC_OK(psf_term(W0, W2));
+    }
     LPC_OK(conv_middle(e, e->gd.S2, e->P, true, g.sh, g.sh + g.H, true));       // D(Hg)
     if (i > 0) head_of(i - 1);
     a.tail = i == 0 ? 1 : 0;
@@ -197,6 +255,7 @@ int gd_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_alp
   e->gd.fwd_done = false;     // S no longer holds the row spectra of the iterate
   LPC_OK(launch_k(e, -1, k_gd_bwd_finish<256>, dim3(C + 1, n), 256, gd_bwd_red_bytes<256>(), (const double*)e->fista.tape_part,
                   e->P, rows, C, (const real*)e->fista.galpha_sched, grad_alpha, grad_coef));
+  if (grad_psf) LPC_OK(gd_bwd_psf_sum(e, e->fista.psf_acc, grad_psf));
   if (grad_init) LPC_OK(planar_to_hwc(e, a.gz, grad_init, e->cfg.batch, g.H, g.W, g.W, g.uplane, 0, 0, 0));
   if (grad_data)
     LPC_OK(launch_k(e, -1, k_gd_bwd_gdata<256>, grid1d(g.uplane, 256, e->cfg.batch), 256, 0, (const real*)a.gb, grad_data,

@@ -4,13 +4,13 @@
 #include "lpc_engine.h"
 #include "lpc_gd_kernels.h"
 
-// one real row per half-length transform (pa: the plan of length Wp / 2): H x rows (e->S) -> residual -> rows (e->gd.S2);
+// one real row per half-length transform (pa: the plan of length Wp / 2): H x rows (Sin) -> residual -> rows (Sout);
 // gradient rows (e->gd.S2) -> fused update of x
 template <int NT, int EM, int SK, class PA>
-static inline int launch_gd_rows_mid_half(Engine* e, const PA& pa) {
+static inline int launch_gd_rows_mid_half(Engine* e, const PA& pa, const real2* Sin, real2* Sout) {
   return launch_k(e, LPC_K_ROW_INV, k_rinv_gd_mid_half<NT, EM, SK, PA>, dim3(e->g.H, e->P), NT,
                   LPC_ROW_SMEM_BYTES(e->g.Wp / 2, SK), geom_rev(e, e->plan.gd_rev_resid), pa, e->planW.tw,
-                  (const real2*)e->S, e->gd.S2, (const real*)e->Y);
+                  Sin, Sout, (const real*)e->Y);
 }
 template <int NT, int EM, int SK, class PA>
 static inline int launch_gd_rows_update_half(Engine* e, const PA& pa, const GdScalars& sc, const real* alpha) {

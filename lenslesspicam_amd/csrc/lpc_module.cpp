@@ -67,17 +67,17 @@ static int m_admm_rows_fwd_x(Engine* e, const AdmmScalars* sc, const K1Rows* k1)
 #endif
 static constexpr int V2SK = LPC_MOD_V2_SK;
 static const size_t kV2Smem = LPC_ROW_SMEM_BYTES(RowP::n, V2SK);
-static int m_gd_rows_mid(Engine* e) {
+static int m_gd_rows_mid(Engine* e, const real2* Sin, real2* Sout) {
   const PlaneGeom& g = e->g;
 #ifndef LPC_DOUBLE
   if constexpr (GdV2<RowP>::ok) {
     if (e->plan.gd_v2)     // second form (lpc_gd_v2_kernels.h): one-radix plan, M / R lanes per row
       return launch_k(e, LPC_K_ROW_INV, k_gd_resid_v2<GdV2<RowP>::NB, V2SK, RowPA>, dim3(g.H, e->P), GdV2<RowP>::NB, kV2Smem,
-                      geom_rev(e, e->plan.gd_rev_resid), row_arg(e), e->planW.tw, (const real2*)e->S, e->gd.S2,
+                      geom_rev(e, e->plan.gd_rev_resid), row_arg(e), e->planW.tw, Sin, Sout,
                       (const real*)e->Y, make_fastdiv((unsigned)g.DC), make_fastdiv((unsigned)g.C));
   }
 #endif
-  return launch_gd_rows_mid_half<RNT, REM, RSK>(e, row_arg(e));
+  return launch_gd_rows_mid_half<RNT, REM, RSK>(e, row_arg(e), Sin, Sout);
 }
 static int m_gd_rows_update(Engine* e, const GdScalars* sc, const real* alpha) {
   return launch_gd_rows_update_half<RNT, REM, RSK>(e, row_arg(e), *sc, alpha);
@@ -106,6 +106,9 @@ static int m_gd_rows_update_fwd(Engine* e, const GdScalars* sc, const real* alph
 static int m_gd_bwd_head(Engine* e, const GdBwd* a) { return launch_gd_bwd_half<0, RNT, REM, RSK>(e, row_arg(e), *a); }
 static int m_gd_bwd_mid(Engine* e, const GdBwd* a) { return launch_gd_bwd_half<1, RNT, REM, RSK>(e, row_arg(e), *a); }
 static int m_gd_bwd_update(Engine* e, const GdBwd* a) { return launch_gd_bwd_half<2, RNT, REM, RSK>(e, row_arg(e), *a); }
+static int m_gd_bwd_acc(Engine* e, const GdBwd* a, const real2* Sin) {
+  return launch_gd_bwd_half<3, RNT, REM, RSK>(e, row_arg(e), *a, Sin);
+}
 #endif
 #endif   // half rows
 
@@ -209,6 +212,7 @@ extern "C" int lpc_module_init(LpcModule* m, size_t engine_size, const char* src
   m->gd_bwd_head = m_gd_bwd_head;
   m->gd_bwd_mid = m_gd_bwd_mid;
   m->gd_bwd_update = m_gd_bwd_update;
+  m->gd_bwd_acc = m_gd_bwd_acc;
 #endif
 #if LPC_MOD_PASSA
   m->cols_passA = m_cols_passA;

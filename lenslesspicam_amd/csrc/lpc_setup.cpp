@@ -186,16 +186,17 @@ int setup_geometry(Engine* e) {
 
 // full forward 2-D transform of a real source into S (used for the PSF and the TV gram)
 int fft2_forward_setup(Engine* e, const RealSrc& src, real2* S, int nplanes) {
-  const PlaneGeom& g = e->g;
   const int zr0 = src.out_row0, zr1 = src.out_row0 + src.nrows;
   LPC_OK(rows_fwd_single(e, src, S, nplanes, -1));
+  return cols_fwd_full(e, S, nplanes, zr0, zr1);
+}
+// the column half of it: row spectra in rows [zr0, zr1) of S (the others count as zero) -> full spectra, in place
+int cols_fwd_full(Engine* e, real2* S, int nplanes, int zr0, int zr1) {
   if (e->plan.N1 > 1) {
     LPC_OK(cols_passA(e, S, nplanes, false, zr0, zr1, -1));
-    LPC_OK(cols_passB_fwd(e, S, nplanes, 0, g.Hp));
-  } else {
-    LPC_OK(cols_passB_fwd(e, S, nplanes, zr0, zr1));
+    return cols_passB_fwd(e, S, nplanes, 0, e->g.Hp);
   }
-  return 0;
+  return cols_passB_fwd(e, S, nplanes, zr0, zr1);
 }
 
 // planar real (padded or not) -> convolution with H / H* -> planar real, same kind

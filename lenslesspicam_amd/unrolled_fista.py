@@ -6,16 +6,24 @@ Unrolled FISTA on the MI355X engine: the iterations of the reference's ``Unrolle
 ``UnrolledFISTA`` is a ``torch.nn.Module`` like the reference's: ``_alpha_p`` (``(n_iter, C)``) and, with
 ``learn_tk``, ``_tk_p`` (``n_iter + 1``) are ``nn.Parameter`` s on the PSF's device, under the reference's names, so
 ``state_dict()`` round-trips with its checkpoints.  ``forward(batch)`` with autograd enabled and any of the parameters,
-``batch`` or the initial estimate requiring a gradient runs as one ``torch.autograd.Function``: the forward is the
+``batch``, the initial estimate or the PSF requiring a gradient runs as one ``torch.autograd.Function``: the forward is the
 inference launch sequence with the handle recording its tape (``lpc_fista_record``), the backward one reverse sweep in
-fused HIP kernels (``lpc_fista_backward``, csrc/lpc_gd_bwd_kernels.h) plus the chain through ``abs`` and
+fused HIP kernels (``lpc_fista_backward`` / ``lpc_fista_backward_psf``, csrc/lpc_gd_bwd_kernels.h) plus the chain through ``abs`` and
 ``(t_i - 1) / t_{i+1}`` on ``n_iter``-sized tensors.  There is one tape per solver: ``backward()`` after a later
 ``forward()`` of the same object raises; a forward without gradients in between keeps the tape's memory
 (``release_tape()`` gives it back).  Not differentiated (``NotImplementedError``, from ``backward()`` for the first two):
-``depth > 1``, frames whose padded height or width is odd, ``proj`` other than ``non_neg``; the PSF gets no gradient.
+``depth > 1``, frames whose padded height or width is odd, ``proj`` other than ``non_neg``.
 
-Pre- / post-processor networks are not taken by the constructor: the measurement gets a gradient, so compose them in
-torch around ``forward()`` -- ``post(rec(pre(batch)))`` trains all three.
+The PSF is an autograd input as well: ``forward(batch, psfs=p)`` with ``p.requires_grad``, or a ``p`` set earlier through
+``_set_psf(p)``, gets ``dL/dp`` in ``p``'s shape, dtype and device from the same reverse sweep (the engine still works on
+its detached device copy).  As in the reference's ``forward(batch, psfs=...)``, which rebuilds the convolver and nothing
+else (``trainable_recon.py:337-350``), the default start value and the steps derived from the constructor's PSF are
+constants.  The gradient costs a workspace of three spectra and one state array on top of the tape (include/lpc.h:
+``lpc_fista_backward_psf``), allocated by the first backward that needs it and given back by ``release_tape()``.  One PSF
+for the batch: per-frame PSFs (a 5-D ``psfs``) raise ``NotImplementedError``.
+
+Pre- / post-processor networks are not taken by the constructor: the measurement and the PSF get gradients, so compose
+them in torch around ``forward()`` -- ``post(rec(pre(batch), psfs=psf + net(psf)))`` trains all of it.
 """
 from __future__ import annotations
 
@@ -28,8 +36,9 @@ from .gd import FISTA, non_neg
 
 class _UnrolledFISTAFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rec, batch, alpha_p, tk_p, init):
+    def forward(ctx, rec, batch, alpha_p, tk_p, init, psf):
         out = rec._run(batch, record=True, push_init=init is not None)
+        ctx.psf_meta = None if psf is None else (tuple(psf.shape), psf.dtype, psf.device)
         ctx.rec, ctx.gen = rec, rec._tape_gen
         ctx.batch_meta = (tuple(batch.shape), batch.dtype, batch.device)
         ctx.init_meta = None if init is None else (tuple(init.shape), init.dtype, init.device)
@@ -50,14 +59,19 @@ class _UnrolledFISTAFunction(torch.autograd.Function):
         if ctx.gen != rec._tape_gen:
             raise RuntimeError("UnrolledFISTA.backward: tape overwritten by a later forward() of the same solver")
         h, n, C = rec._handle, rec._n_iter, int(rec._psf_shape[3])
-        need_b, need_a, need_t, need_i = ctx.needs_input_grad[1:5]
+        need_b, need_a, need_t, need_i, need_p = ctx.needs_input_grad[1:6]
         g = rec._to_dev(grad_out)
         bshape = ctx.batch_meta[0]
         g_data = rec._empty((bshape[0],) + bshape[2:]) if need_b else None
         g_init = rec._empty(tuple(g.shape)) if need_i else None
         g_a, g_c = rec._empty((n, C)), rec._empty((n,))
-        h.fista_backward(g.data_ptr(), None if g_data is None else g_data.data_ptr(), g_a.data_ptr(), g_c.data_ptr(),
-                         None if g_init is None else g_init.data_ptr(), rec._stream())
+        g_psf = rec._empty(tuple(int(v) for v in rec._psf_shape)) if need_p else None
+        ptrs = (g.data_ptr(), None if g_data is None else g_data.data_ptr(), g_a.data_ptr(), g_c.data_ptr(),
+                None if g_init is None else g_init.data_ptr())
+        if need_p:
+            h.fista_backward_psf(*ptrs, g_psf.data_ptr(), rec._stream())
+        else:
+            h.fista_backward(*ptrs, rec._stream())
         # through |.| and c_i = (t_i - 1) / t_{i+1}, formed as _push_schedule forms them
         with torch.enable_grad():
             ap = alpha_p.detach().requires_grad_(need_a)
@@ -65,14 +79,17 @@ class _UnrolledFISTAFunction(torch.autograd.Function):
             alpha, coef = rec._schedule_of(ap, tp)
             ga = torch.autograd.grad(alpha, ap, g_a.to(device=alpha.device, dtype=alpha.dtype))[0] if need_a else None
             gt = torch.autograd.grad(coef, tp, g_c.to(device=coef.device, dtype=coef.dtype))[0] if need_t else None
-        gb = gi = None
+        gb = gi = gp = None
         if need_b:
             gb = g_data[:, None].to(device=ctx.batch_meta[2], dtype=ctx.batch_meta[1])
         if need_i:
             shape, dtype, device = ctx.init_meta
             gi = g_init if shape[0] == g_init.shape[0] else g_init.sum(0, keepdim=True)     # one estimate for the batch
             gi = gi.reshape(shape).to(device=device, dtype=dtype)
-        return None, gb, ga, gt, gi
+        if need_p:
+            shape, dtype, device = ctx.psf_meta
+            gp = g_psf.reshape(shape).to(device=device, dtype=dtype)
+        return None, gb, ga, gt, gi, gp
 
 
 class UnrolledFISTA(FISTA, torch.nn.Module):
@@ -170,13 +187,17 @@ class UnrolledFISTA(FISTA, torch.nn.Module):
         if background is not None:
             raise NotImplementedError("background subtraction networks are outside the hot path")
         if psfs is not None:
+            if isinstance(psfs, torch.Tensor) and psfs.dim() == 5:
+                raise NotImplementedError("UnrolledFISTA: per-frame PSFs (a 5-D psfs) are not implemented: one PSF "
+                                          "for the batch")
             self._set_psf(psfs)
         init = self._initial_est if isinstance(self._initial_est, torch.Tensor) else None
+        psf = self._psf if isinstance(self._psf, torch.Tensor) and self._psf.requires_grad else None
         if torch.is_grad_enabled() and any(t is not None and t.requires_grad
-                                           for t in (batch, self._alpha_p, self._tk_p, init)):
+                                           for t in (batch, self._alpha_p, self._tk_p, init, psf)):
             if self._hook:
                 raise NotImplementedError("UnrolledFISTA: only proj=non_neg is differentiated")
             if init is not None and not init.requires_grad:
                 init = None
-            return _UnrolledFISTAFunction.apply(self, batch, self._alpha_p, self._tk_p, init)
+            return _UnrolledFISTAFunction.apply(self, batch, self._alpha_p, self._tk_p, init, psf)
         return self._run(batch)

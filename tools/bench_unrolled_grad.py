@@ -2,14 +2,17 @@
 """
 Times one training step of UnrolledFISTA on the MI355X: DiffuserCam-sized frames (270 x 480 x 3), B = 8, float32.
 
-    python tools/bench_unrolled_grad.py [--n 5 20] [--reps 30] [--package-root DIR] [--once]
+    python tools/bench_unrolled_grad.py [--n 5 20] [--reps 30] [--package-root DIR] [--once] [--psf-grad]
 
 Legs, each with warm-up and HIP events around every repetition (median, min, max in ms):
   (a) forward() under no_grad                       (--package-root: the same call on another checkout, e.g. the parent)
   (b) forward() with gradients: the recorded forward
   (c) backward() of (out * w).sum()
   (d) the same gradients from torch.autograd over a torch.fft restatement of the iteration, forward + backward
---once: one recorded forward + backward per n and nothing else (for a kernel trace).
+--psf-grad adds the PSF as a leaf (``rec._set_psf(p)`` once, ``p.requires_grad``):
+  (e) backward() with the PSF gradient (its recorded forward is (b)'s)
+  (f) torch.autograd over the restatement with the PSF as a leaf as well, forward + backward
+--once: one recorded forward + backward per n and nothing else (for a kernel trace; with --psf-grad: with the PSF gradient).
 Prints one JSON line per n.
 """
 import argparse
@@ -26,6 +29,7 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--package-root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--once", action="store_true")
+    ap.add_argument("--psf-grad", action="store_true")
     args = ap.parse_args()
     sys.path.insert(0, args.package_root)
     import numpy as np
@@ -66,12 +70,15 @@ def main():
     sh, sw = (Hp - H) // 2, (Wp - W) // 2
     Hs = torch.fft.rfft2(torch.nn.functional.pad(psf, (0, 0, sw, Wp - W - sw, sh, Hp - H - sh)), norm="ortho", dim=(-3, -2))
 
-    def conv(x, adj):
-        X = torch.fft.rfft2(torch.nn.functional.pad(x, (0, 0, sw, Wp - W - sw, sh, Hp - H - sh)), dim=(-3, -2))
-        y = torch.fft.ifftshift(torch.fft.irfft2(X * (Hs.conj() if adj else Hs), dim=(-3, -2), s=(Hp, Wp)), dim=(-3, -2))
-        return y[..., sh:sh + H, sw:sw + W, :]
+    def spectrum(p):
+        return torch.fft.rfft2(torch.nn.functional.pad(p, (0, 0, sw, Wp - W - sw, sh, Hp - H - sh)), norm="ortho", dim=(-3, -2))
 
-    def restated(batch, alpha_p, tk_p, n):
+    def restated(batch, alpha_p, tk_p, n, Hs=Hs):
+        def conv(x, adj):
+            X = torch.fft.rfft2(torch.nn.functional.pad(x, (0, 0, sw, Wp - W - sw, sh, Hp - H - sh)), dim=(-3, -2))
+            y = torch.fft.ifftshift(torch.fft.irfft2(X * (Hs.conj() if adj else Hs), dim=(-3, -2), s=(Hp, Wp)), dim=(-3, -2))
+            return y[..., sh:sh + H, sw:sw + W, :]
+
         flat = psf.reshape(-1, C)
         y = (torch.ones_like(psf[None]) * ((flat.max(0).values + flat.min(0).values) / 2)).expand(B, -1, -1, -1, -1)
         xk = y
@@ -88,6 +95,8 @@ def main():
                "plan": rec._handle.plan_info() if hasattr(rec._handle, "plan_info") else ""}
         batch = data.clone().requires_grad_(trainable)
         if args.once:
+            if args.psf_grad:
+                rec._set_psf(psf.clone().requires_grad_())
             (rec(batch) * w).sum().backward()
             torch.cuda.synchronize()
             continue
@@ -118,6 +127,20 @@ def main():
             res["b_plus_c_ms"] = round(bc, 4)
             res["c_over_a"] = round(res["c_backward_ms"]["median"] / res["a_forward_no_grad_ms"]["median"], 3)
             res["d_over_b_plus_c"] = round(res["d_torch_autograd_fwd_bwd_ms"]["median"] / bc, 3)
+            if args.psf_grad:
+                pe, pl = psf.clone().requires_grad_(), psf.clone().requires_grad_()
+                rec._set_psf(pe)
+                res["e_backward_psf_ms"] = timed(lambda: state["loss"].backward(), setup=fwd)
+                res["f_torch_autograd_psf_fwd_bwd_ms"] = timed(
+                    lambda: (restated(bt, ap, tp, n, spectrum(pl)) * w).sum().backward())
+                pe.grad = pl.grad = None
+                (rec(batch) * w).sum().backward()
+                (restated(bt, ap, tp, n, spectrum(pl)) * w).sum().backward()
+                res["check_rel_g_psf"] = float((pe.grad - pl.grad).abs().max() / pl.grad.abs().max())
+                assert res["check_rel_g_psf"] < 1e-4, res
+                res["e_over_c"] = round(res["e_backward_psf_ms"]["median"] / res["c_backward_ms"]["median"], 3)
+                be = res["b_recorded_forward_ms"]["median"] + res["e_backward_psf_ms"]["median"]
+                res["f_over_b_plus_e"] = round(res["f_torch_autograd_psf_fwd_bwd_ms"]["median"] / be, 3)
         print(json.dumps(res), flush=True)
 
 
