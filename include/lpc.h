@@ -173,6 +173,12 @@ int lpc_reset(lpc_handle h, void* stream);
 /* Nesterov: overrides (p, mu) like NesterovGradientDescent.reset(p, mu) gd.py:178-181;
  * FISTA: overrides tk like FISTA.reset(tk) gd.py:227-233.  Call after lpc_reset. */
 int lpc_set_momentum(lpc_handle h, double p, double mu, double tk);
+/* GD family: pins the default start value, dev_start: C values on the device (what lpc_get_state "start_value" wrote).
+ * From then on lpc_set_psf leaves it alone -- the reference's UnrolledFISTA computes `_image_init` once, from the
+ * constructor's PSF (unrolled_fista.py:55-59), and forward(batch, psfs=...) / _set_psf() restart from it whatever PSF is
+ * current.  NULL: the start value follows the PSF again from the next lpc_set_psf on (gd.py:100-105).  Takes effect at the
+ * next lpc_reset(); allocates nothing; an initial estimate (lpc_set_initial_estimate) still wins. */
+int lpc_set_start_value(lpc_handle h, const lpc_real* dev_start, void* stream);
 
 /* Unrolled ADMM (lensless/recon/unrolled_admm.py:133-234): iteration i (counted from the last reset)
  * uses mu1[i], mu2[i], mu3[i], tau[i]; the last entry is held beyond n.  n <= 0 clears the schedule and
@@ -268,7 +274,7 @@ int lpc_form_image(lpc_handle h, lpc_real* dev_out, void* stream);
 /* inspection (tests, warm starts).  name: "image_est" (solver state shape), and for ADMM
  * "X","xi","rho","forward_out","W" as (B,D,Hp,Wp,C), "U","eta" as (B,D,Hp,Wp,C,2)
  * [values as the reference holds them after the same number of iterations].
- * GD family: "alpha" writes C floats. */
+ * GD family: "alpha" and "start_value" (the default start value per channel) write C floats. */
 int lpc_get_state(lpc_handle h, const char* name, lpc_real* dev_out, void* stream);
 
 /* ---- evaluation reductions on the device (no host synchronisation of the results) -------------- */

@@ -117,6 +117,7 @@ class Lib:
             "lpc_set_initial_estimate": [vp, fp, vp],
             "lpc_reset": [vp, vp],
             "lpc_set_momentum": [vp, C.c_double, C.c_double, C.c_double],
+            "lpc_set_start_value": [vp, fp, vp],
             "lpc_iterate": [vp, C.c_int, vp],
             "lpc_admm_pnp_begin": [vp, C.c_int, fp, vp],
             "lpc_admm_pnp_end": [vp, C.c_int, fp, vp],
@@ -255,6 +256,10 @@ class Handle:
 
     def set_momentum(self, p=0.0, mu=0.9, tk=0.0):
         self._c(self.lib.dll.lpc_set_momentum(self.h, p, mu, tk))
+
+    def set_start_value(self, ptr, stream=0):
+        """pins the GD family's default start value to the C device values at ``ptr`` (None: it follows the PSF again)"""
+        self._c(self.lib.dll.lpc_set_start_value(self.h, ptr, stream))
 
     def set_admm_schedule(self, mu1, mu2, mu3, tau):
         n = len(mu1)

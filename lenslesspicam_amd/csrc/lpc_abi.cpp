@@ -178,6 +178,15 @@ int lpc_set_momentum(lpc_handle e, double p, double mu, double tk) {
   return gd_apply_momentum_reset(e);
 }
 
+int lpc_set_start_value(lpc_handle e, const real* dev_start, void* stream) {
+  if (!e) return fail("null handle");
+  if (e->cfg.algo < LPC_ALGO_GD) return fail("lpc_set_start_value: gradient-descent family only");
+  e->stream = (lpcStream_t)stream;
+  e->gd.gx0_pinned = dev_start != nullptr;
+  if (dev_start) LPC_RT(rt::copy_d2d_async(e->gd.gx0, dev_start, e->cfg.channels * sizeof(real), e->stream));
+  return 0;
+}
+
 int lpc_set_admm_schedule(lpc_handle e, int n, const double* mu1, const double* mu2, const double* mu3,
                           const double* tau) {
   if (!e) return fail("null handle");

@@ -167,6 +167,7 @@ struct GdState {
   real *gx = nullptr, *gaux = nullptr;  // x and (p | xk_prev)
   real* galpha = nullptr;               // [C] device
   real* gx0 = nullptr;                  // [C] default start value per channel
+  bool gx0_pinned = false;              // lpc_set_start_value: lpc_set_psf leaves gx0 alone
   real2* S2 = nullptr;                  // second spectrum buffer (row-inverse+forward is out of place)
   double tk = 1.0, nest_mu = 0.9, nest_p = 0.0;
   bool fwd_done = false;       // the row spectra of H x's input are already in S (written by the fused update kernel)

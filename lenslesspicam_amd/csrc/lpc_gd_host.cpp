@@ -23,6 +23,7 @@ int gd_setup_constants(Engine* e) {
   LPC_OK(plane_minmax(e, e->Hs, nullptr, nblk, e->Ppsf, partial));
   LPC_OK(launch_k(e, -1, k_channel_finish, dim3(1), 64, 0, (const real*)partial, nblk, e->cfg.depth,
                   e->cfg.channels, 0, (real)e->cfg.lip_fact, e->gd.galpha));
+  if (e->gd.gx0_pinned) return 0;   // unrolled FISTA: the constructor's start value stays (unrolled_fista.py:55-59)
   LPC_OK(plane_minmax(e, nullptr, e->psf_planar, nblk, e->Ppsf, partial));
   LPC_OK(launch_k(e, -1, k_channel_finish, dim3(1), 64, 0, (const real*)partial, nblk, e->cfg.depth,
                   e->cfg.channels, 1, (real)0., e->gd.gx0));
@@ -285,8 +286,8 @@ int gd_get_state(Engine* e, const std::string& nm, real* dev_out) {
   const PlaneGeom& g = e->g;
   const int nimg = e->cfg.batch * e->cfg.depth;
   if (nm == "image_est") return planar_to_hwc(e, e->gd.gx, dev_out, nimg, g.H, g.W, g.W, g.uplane, 0, 0, 0);
-  if (nm == "alpha") {
-    LPC_RT(rt::copy_d2d_async(dev_out, e->gd.galpha, e->cfg.channels * sizeof(real), e->stream));
+  if (nm == "alpha" || nm == "start_value") {
+    LPC_RT(rt::copy_d2d_async(dev_out, nm == "alpha" ? e->gd.galpha : e->gd.gx0, e->cfg.channels * sizeof(real), e->stream));
     return 0;
   }
   return fail("lpc_get_state: unknown name '" + nm + "'");

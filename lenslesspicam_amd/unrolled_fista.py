@@ -113,6 +113,17 @@ class UnrolledFISTA(FISTA, torch.nn.Module):
         self._sched_key = None
         self._tape_gen = 0
         self._rec_state = (None, False)
+        # unrolled_fista.py:55-59: `_image_init` is computed here, from this PSF, and reset() (:91-96) reuses it whatever PSF
+        # forward(batch, psfs=...) or _set_psf() made current since -- unlike gd.py:94-112, which follows the PSF.  The
+        # handle computed it in lpc_set_psf; every handle of this solver is pinned to these values.
+        self._start_dev = self._empty((C,))
+        self._handle.get_state("start_value", self._start_dev.data_ptr(), self._stream())
+        self._handle.set_start_value(self._start_dev.data_ptr(), self._stream())
+
+    def _after_new_handle(self):
+        super()._after_new_handle()
+        self._handle.set_start_value(self._start_dev.data_ptr(), self._stream())
+        self._handle.reset(self._stream())      # (lpc_set_psf reset this handle before the start value was pinned)
 
     def set_parameters(self, alpha=None, tk=None):
         with torch.no_grad():

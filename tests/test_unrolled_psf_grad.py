@@ -5,8 +5,10 @@ Gradient of unrolled FISTA with respect to the PSF (lpc_fista_backward_psf; ``Un
 
 Inputs: the cases of tests/test_unrolled_grad_sweep.py (signed measurement; every projection kink-free and 20 - 80 %
 clamped, asserted there in ``inputs``; the forward pass is that sweep's).  Reference: ``restated()`` with the PSF as a leaf and
-``init`` passed explicitly, computed from the DETACHED PSF -- the default start value (max psf + min psf) / 2 is a constant
-in the reference's ``forward(batch, psfs=...)``, which rebuilds the convolver and nothing else -- loss ``(out * w).sum()``.
+``init`` passed explicitly, computed from the DETACHED PSF -- the default start value is a constant in the reference's
+``forward(batch, psfs=...)``, which rebuilds the convolver and nothing else: it stays (max + min) / 2 of the CONSTRUCTOR's
+PSF.  Every ``psfs`` here has the constructor's values, so the two coincide; tests/test_psf_swap.py passes another PSF and
+tells them apart -- loss ``(out * w).sum()``.
 The restatement with a PSF leaf is itself pinned to the reference's own ``psfs`` gradient
 (tests/golden/gen_unrolled_psf_grad.py, test_restatement_with_psf_leaf_is_pinned).
 
@@ -209,7 +211,8 @@ def test_both_ways_in(backend, how):
 
 def test_psf_correction_network_trains(backend):
     """``rec(batch, psfs=psf + net(psf))`` with a one-parameter net: the parameter's gradient is autograd's over the
-    restatement (float64 build)"""
+    restatement (float64 build), started like the reference's from the default of the CONSTRUCTOR's PSF (the net changes the
+    PSF's maximum: unrolled_fista.py:55-59, tests/test_psf_swap.py)"""
     inp = inputs("12x30")
     dev = backend.device
     psf = torch.from_numpy(inp.psf).double()
@@ -226,7 +229,7 @@ def test_psf_correction_network_trains(backend):
     rtheta = torch.tensor(0.3, dtype=torch.float64, requires_grad=True)
     eff = psf + net(rtheta, psf)
     rout, _ = restated(eff, torch.from_numpy(inp.data), torch.from_numpy(inp.alpha).double(), torch.from_numpy(inp.tk), inp.n,
-                       init=default_init(eff))
+                       init=default_init(psf))
     (rout * w).sum().backward()
     assert theta.grad is not None and theta.grad.shape == theta.shape
     r = abs(float(theta.grad) - float(rtheta.grad)) / abs(float(rtheta.grad))
