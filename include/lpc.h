@@ -228,6 +228,35 @@ int lpc_fista_backward_psf(lpc_handle h, const lpc_real* dev_grad_out, lpc_real*
                            lpc_real* dev_grad_psf,    /* (D,H,W,C): w.r.t. the PSF                               */
                            void* stream);
 
+/* Reverse mode of the unrolled ADMM iterations (unrolled_admm.py:181-234 differentiated; what torch.autograd does in the
+ * reference's training loop).  ADMM handles with a schedule (lpc_set_admm_schedule) only.
+ * lpc_admm_record(h, 1): from the next lpc_reset on, lpc_iterate keeps the iterates V_0 .. V_n -- the launch plan's own
+ * kernels plus one device copy per iteration, so the recorded forward has the bits of the unrecorded one.  Nothing a launch
+ * plan keeps in its own form (H V outside the window, xi, half-applied duals) is taped: lpc_admm_backward first replays
+ * H V_i and the duals of every iteration from the iterates, so the tape is the same for every plan.  For a schedule of n
+ * iterations the tape is ONE allocation, counted in lpc_workspace_bytes,
+ *   (6 n + 11) * P * Hp * rpitch * sizeof(lpc_real)  +  n * P * ceil(Hp / 8) * ceil(Wp / 128) * 4 * sizeof(double)   bytes,
+ * P = B * C planes, rpitch = Wp rounded up to a multiple of 4 (Hp, Wp: lpc_padded_shape): V_i and H V_i (2 n + 2 arrays),
+ * xi, eta (two components) and rho of every iteration (4 n), 8 work arrays of the sweep, the data gradient, and the partial
+ * sums of the four reductions.  lpc_admm_record(h, 0) frees it (this waits for the stream); lpc_admm_record(h, -1) pauses:
+ * nothing is recorded from the next lpc_reset on, the tape stays allocated.  lpc_set_admm_schedule, lpc_set_data and
+ * lpc_set_psf invalidate what was recorded.
+ * lpc_admm_backward: given dL/d(clip(crop(V_n), 0)) -- the (B,D,H,W,C) image UnrolledADMM returns, unrolled_admm.py:236-240
+ * -- it writes the gradients w.r.t. the measurement and the mu1[], mu2[], mu3[], tau[] given to lpc_set_admm_schedule (n
+ * values each).  Per iteration: one spectral step of the forward's own (on every plan the form lpc_admm_pnp_end uses) and
+ * one fused image-domain kernel; all four parameter gradients are image-domain dot products.  Asynchronous on `stream`,
+ * device memory only, no atomics: a second call gives the same bits; the tape and the solver state stay intact.  It
+ * fails, with a message, when: the handle is not an ADMM handle / has no schedule / has nothing recorded; the iterations
+ * since the reset are not exactly the schedule's; depth > 1; the padded height or width is odd (the spectral step and the
+ * convolve / deconvolve pair are self-adjoint for even padded lengths only); lpc_set_psi_gram replaced the prior or the
+ * handle runs plug-and-play iterations; an initial estimate is set. */
+int lpc_admm_record(lpc_handle h, int on);
+int lpc_admm_backward(lpc_handle h, const lpc_real* dev_grad_out,   /* (B,D,H,W,C)                                   */
+                      lpc_real* dev_grad_data,    /* (B,H,W,data_channels) or NULL                             */
+                      lpc_real* dev_grad_mu1, lpc_real* dev_grad_mu2, lpc_real* dev_grad_mu3,
+                      lpc_real* dev_grad_tau,     /* n values each                                             */
+                      void* stream);
+
 /* ---- the hot loop: `for i in range(n_iter): self._update(i)`  recon.py:575-576 ------ */
 /* exactly n_iter iterations, asynchronous on `stream`; no early exit exists on this path */
 int lpc_iterate(lpc_handle h, int n_iter, void* stream);

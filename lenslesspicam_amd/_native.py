@@ -131,6 +131,8 @@ class Lib:
             "lpc_fista_record": [vp, C.c_int],
             "lpc_fista_backward": [vp, fp, fp, fp, fp, fp, vp],
             "lpc_fista_backward_psf": [vp, fp, fp, fp, fp, fp, fp, vp],
+            "lpc_admm_record": [vp, C.c_int],
+            "lpc_admm_backward": [vp, fp, fp, fp, fp, fp, fp, vp],
             "lpc_form_image": [vp, fp, vp],
             "lpc_get_state": [vp, C.c_char_p, fp, vp],
             "lpc_profile_enable": [vp, C.c_int],
@@ -290,6 +292,16 @@ class Handle:
         (lpc_fista_backward_psf)"""
         self._c(self.lib.dll.lpc_fista_backward_psf(self.h, grad_out_ptr, grad_data_ptr, grad_alpha_ptr, grad_coef_ptr,
                                                     grad_init_ptr, grad_psf_ptr, stream))
+
+    def admm_record(self, on=True):
+        """the tape of the unrolled ADMM iterates from the next ``reset`` on (lpc_admm_record): True / 1 keep it,
+        False / 0 free it, -1 stop recording but keep the memory"""
+        self._c(self.lib.dll.lpc_admm_record(self.h, int(on)))
+
+    def admm_backward(self, grad_out_ptr, grad_data_ptr, grad_mu1_ptr, grad_mu2_ptr, grad_mu3_ptr, grad_tau_ptr, stream=0):
+        """replay + reverse sweep over the tape: device pointers; ``grad_data_ptr`` may be None (lpc_admm_backward)"""
+        self._c(self.lib.dll.lpc_admm_backward(self.h, grad_out_ptr, grad_data_ptr, grad_mu1_ptr, grad_mu2_ptr,
+                                               grad_mu3_ptr, grad_tau_ptr, stream))
 
     def clear_admm_schedule(self):
         self._c(self.lib.dll.lpc_set_admm_schedule(self.h, 0, None, None, None, None))

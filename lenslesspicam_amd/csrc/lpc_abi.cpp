@@ -143,6 +143,7 @@ int lpc_set_data(lpc_handle e, const real* dev_data, int data_channels, void* st
   e->data_set = true;
   e->data_channels = data_channels;
   e->fista.tape_iters = -1;      // a tape recorded with other data no longer matches (lpc_fista_backward refuses)
+  e->atape.tape_iters = -1;      // ... and lpc_admm_backward
   return 0;
 }
 
@@ -192,6 +193,7 @@ int lpc_set_admm_schedule(lpc_handle e, int n, const double* mu1, const double* 
   if (!e) return fail("null handle");
   if (e->cfg.algo != LPC_ALGO_ADMM) return fail("lpc_set_admm_schedule: not an ADMM handle");
   for (auto& v : e->admm.sched) v.clear();
+  e->atape.tape_iters = -1;      // a tape recorded with another schedule no longer matches (lpc_admm_backward refuses)
   if (n <= 0) return 0;
   if (!mu1 || !mu2 || !mu3 || !tau) return fail("lpc_set_admm_schedule: null array");
   for (int i = 0; i < n; ++i) {
@@ -248,6 +250,41 @@ int lpc_fista_backward(lpc_handle e, const real* dev_grad_out, real* dev_grad_da
 int lpc_fista_backward_psf(lpc_handle e, const real* dev_grad_out, real* dev_grad_data, real* dev_grad_alpha,
                            real* dev_grad_coef, real* dev_grad_init, real* dev_grad_psf, void* stream) {
   return fista_backward(e, dev_grad_out, dev_grad_data, dev_grad_alpha, dev_grad_coef, dev_grad_init, dev_grad_psf, stream);
+}
+
+int lpc_admm_record(lpc_handle e, int on) {
+  if (!e) return fail("null handle");
+  if (e->cfg.algo != LPC_ALGO_ADMM) return fail("lpc_admm_record: not an ADMM handle");
+  e->atape.rec_on = on > 0;
+  e->atape.tape_iters = -1;
+  if (on < 0) return 0;                                    // pause: the tape stays allocated, nothing is recorded
+  if (!e->atape.rec_on) { admm_tape_free(e); return 0; }
+  return e->admm.sched[0].empty() ? 0 : admm_tape_alloc(e);     // (no schedule yet: lpc_reset allocates)
+}
+
+int lpc_admm_backward(lpc_handle e, const real* dev_grad_out, real* dev_grad_data, real* dev_grad_mu1, real* dev_grad_mu2,
+                      real* dev_grad_mu3, real* dev_grad_tau, void* stream) {
+  if (!e || !dev_grad_out || !dev_grad_mu1 || !dev_grad_mu2 || !dev_grad_mu3 || !dev_grad_tau)
+    return fail("lpc_admm_backward: null argument");
+  if (e->cfg.algo != LPC_ALGO_ADMM) return fail("lpc_admm_backward: not an ADMM handle");
+  const long n = (long)e->admm.sched[0].size();
+  if (n <= 0) return fail("lpc_admm_backward: the handle has no schedule (lpc_set_admm_schedule)");
+  if (e->cfg.depth > 1) return fail("lpc_admm_backward: depth > 1 is not implemented");
+  if ((e->g.Hp | e->g.Wp) & 1)
+    return fail("lpc_admm_backward: padded frame " + std::to_string(e->g.Hp) + " x " + std::to_string(e->g.Wp) +
+                " has an odd length: the spectral step and the convolve / deconvolve pair are not self-adjoint there "
+                "(not implemented)");
+  if (e->admm.custom_gram || e->admm.pnp_mode)
+    return fail("lpc_admm_backward: a caller's psi and plug-and-play iterations are not differentiated");
+  if (e->has_init) return fail("lpc_admm_backward: an initial estimate is set (its gradient is not implemented)");
+  if (!e->atape.rec_on || !e->atape.tape || e->atape.tape_iters < 0)
+    return fail("lpc_admm_backward: nothing recorded (lpc_admm_record(h, 1), then lpc_reset and lpc_iterate)");
+  if (e->iters_done != n || e->atape.tape_iters != n || e->atape.tape_n != n)
+    return fail("lpc_admm_backward: " + std::to_string(e->iters_done) + " iterations since the reset, the schedule has " +
+                std::to_string(n));
+  if (dev_grad_data && !e->data_set) return fail("lpc_admm_backward: no data set");
+  e->stream = (lpcStream_t)stream;
+  return admm_backward(e, dev_grad_out, dev_grad_data, dev_grad_mu1, dev_grad_mu2, dev_grad_mu3, dev_grad_tau);
 }
 
 int lpc_iterate(lpc_handle e, int n_iter, void* stream) {

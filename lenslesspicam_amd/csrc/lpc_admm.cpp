@@ -112,6 +112,7 @@ int admm_setup_constants(Engine* e) {
   LPC_OK(fft2_forward_setup(e, src_padded(e, stencil), Gs, 1));
   LPC_OK(launch_k(e, -1, k_abs_complex<256>, grid1d((long)g.cplane, 256), 256, 0, (const real2*)Gs, e->admm.Gabs,
                   (long)g.cplane));
+  e->admm.custom_gram = false;
   return admm_split_gram(e);
 }
 
@@ -133,7 +134,7 @@ int admm_reset(Engine* e) {
   e->first = true;
   e->admm.pnp_mode = e->admm.pnp_pending = false;
   e->iters_done = 0;
-  return 0;
+  return admm_tape_reset(e);
 }
 
 // (r_sp, a) in e->admm.Rsp / e->admm.Aarr  ->  Vout = irfft2(R_div (rfft2 r_sp + s H* rfft2 a)),  HVout = H Vout:
@@ -144,6 +145,10 @@ static int admm_spectral_step(Engine* e, const AdmmScalars& sc, real* Vout, real
   else LPC_OK(admm_rows_fwd(e));
   LPC_OK(admm_cols(e, sc));
   return admm_rows_inv(e, Vout, HVout, sc.skiphv != 0);
+}
+// ... with the step sizes `par` and nothing skipped: the spectral step of the reverse sweep (lpc_admm_bwd.cpp)
+int admm_spectral_plain(Engine* e, const double par[4], real* Vout, real* HVout) {
+  return admm_spectral_step(e, admm_scalars(e, par), Vout, HVout);
 }
 
 
@@ -208,6 +213,7 @@ int admm_iterate(Engine* e, int n_iter) {
     e->admm.hcur ^= 1;  // ... and the other H V buffer its forward model
     sb_rows_valid = true;   // the inverse column passes of this step left rfft(H V row) / Wp in every row of SB
     for (int k = 0; k < 4; ++k) e->admm.last_par[k] = par[k];
+    LPC_OK(admm_tape_push(e, Vo));     // (recording: a stream-ordered copy; the kernels are the unrecorded forward's)
     ++e->iters_done;
   }
   return 0;
@@ -262,6 +268,7 @@ int admm_set_psi_gram(Engine* e, const real* dev_gabs) {
   LPC_RT(rt::memset_async(e->admm.Gabs, 0, (size_t)g.cplane * sizeof(real), e->stream));
   LPC_OK(launch_k(e, -1, k_permute_spectrum_rows<256>, grid1d((long)g.Hp * g.Wc, 256), 256, 0, dev_gabs, e->admm.Gabs, g.Hp,
                   g.Wc, g.cpitch, e->plan.N1, e->plan.N2));
+  e->admm.custom_gram = true;
   return admm_split_gram(e);
 }
 

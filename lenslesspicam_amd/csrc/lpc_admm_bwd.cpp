@@ -1,0 +1,131 @@
+// lpc_admm_bwd.cpp -- reverse mode of unrolled ADMM (lpc_admm_record / lpc_admm_backward): the tape of iterates, the
+// replay that rebuilds H V and the duals of every iteration from it, and the reverse sweep.  The image-domain kernels are
+// lpc_admm_bwd_kernels.h; the spectral step of the sweep is the forward's own (lpc_admm.cpp: admm_spectral_plain).
+#include "lpc_engine.h"
+#include "lpc_admm_bwd_kernels.h"
+#include "lpc_gd_bwd_kernels.h"      // k_gd_bwd_gdata: planar data gradient -> the measurement's layout
+
+static constexpr int kBwdTH = 8, kBwdQW = 32;      // k_admm_bwd_step: tiles of 8 rows x 128 columns on 256 lanes
+static inline long bwd_tiles_x(const PlaneGeom& g) { return (g.Wp + 4 * kBwdQW - 1) / (4 * kBwdQW); }
+static inline long bwd_tiles(const PlaneGeom& g) { return bwd_tiles_x(g) * ((g.Hp + kBwdTH - 1) / kBwdTH); }
+
+void admm_tape_free(Engine* e) {
+  AdmmTape& t = e->atape;
+  if (!t.tape) return;
+  dev_free(e, t.tape);
+  dev_free(e, t.part);
+  t.tape = nullptr; t.part = nullptr; t.tape_n = 0; t.tape_iters = -1;
+}
+
+int admm_tape_alloc(Engine* e) {
+  AdmmTape& t = e->atape;
+  const int n = (int)e->admm.sched[0].size();
+  if (t.tape && t.tape_n == n) return 0;
+  admm_tape_free(e);
+  const size_t rp = (size_t)e->g.rplane * e->P;
+  LPC_OK(dev_alloc(e, &t.tape, (size_t)(6 * n + 11) * rp));
+  if (dev_alloc(e, &t.part, (size_t)n * e->P * bwd_tiles(e->g) * 4)) {      // all or nothing
+    admm_tape_free(e);
+    return 1;
+  }
+  t.tape_n = n;
+  return 0;
+}
+
+// slots of the tape, in padded state arrays (AdmmTape)
+static inline real* tape_slot(Engine* e, long k) { return e->atape.tape + (size_t)k * e->g.rplane * e->P; }
+static inline real* tape_v(Engine* e, int i) { return tape_slot(e, i); }
+static inline real* tape_hv(Engine* e, int i) { return tape_slot(e, e->atape.tape_n + 1 + i); }
+static inline real* tape_dual(Engine* e, int which, int i) {      // which: 0 xi, 1 eta0, 2 eta1, 3 rho
+  return tape_slot(e, 2 * (e->atape.tape_n + 1) + (long)which * e->atape.tape_n + i);
+}
+static inline real* tape_work(Engine* e, int k) { return tape_slot(e, 6 * e->atape.tape_n + 2 + k); }
+
+int admm_tape_reset(Engine* e) {
+  AdmmTape& t = e->atape;
+  t.tape_iters = -1;
+  // (an initial estimate, a caller's psi and plug-and-play iterations are not differentiated: nothing is recorded, and
+  // lpc_admm_backward says why)
+  if (!t.rec_on || e->admm.sched[0].empty() || e->has_init) return 0;
+  LPC_OK(admm_tape_alloc(e));
+  LPC_RT(rt::memset_async(tape_v(e, 0), 0, (size_t)e->g.rplane * e->P * sizeof(real), e->stream));     // V_0
+  t.tape_iters = 0;
+  return 0;
+}
+
+int admm_tape_push(Engine* e, const real* Vnew) {
+  AdmmTape& t = e->atape;
+  if (t.tape_iters < 0 || t.tape_iters != e->iters_done || e->iters_done >= t.tape_n) return 0;
+  LPC_RT(rt::copy_d2d_async(tape_v(e, (int)e->iters_done + 1), Vnew, (size_t)e->g.rplane * e->P * sizeof(real), e->stream));
+  ++t.tape_iters;
+  return 0;
+}
+
+static AdmmBwdScalars bwd_scalars(const Engine* e, int i, int n) {
+  const std::vector<double>* s = e->admm.sched;
+  AdmmBwdScalars p;
+  p.m1 = (real)s[0][i]; p.m2 = (real)s[1][i]; p.m3 = (real)s[2][i];
+  p.thr = (real)(s[3][i] / s[1][i]);
+  p.m_in = (real)(1.0 / (1.0 + s[0][i])); p.m_out = (real)(1.0 / s[0][i]);
+  p.r_m2 = (real)(1.0 / s[1][i]); p.r_m3 = (real)(1.0 / s[2][i]);
+  p.pre = i > 0 ? 1 : 0;
+  p.n1 = p.pre ? (real)s[0][i - 1] : (real)0.; p.n2 = p.pre ? (real)s[1][i - 1] : (real)0.;
+  p.n3 = p.pre ? (real)s[2][i - 1] : (real)0.;
+  p.gb_first = i == n - 1 ? 1 : 0;
+  return p;
+}
+
+int admm_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_mu1, real* grad_mu2, real* grad_mu3,
+                  real* grad_tau) {
+  const PlaneGeom& g = e->g;
+  const int n = e->atape.tape_n;
+  const size_t rb_bytes = (size_t)g.rplane * e->P * sizeof(real);
+  const dim3 pw = grid1d((long)g.Hp * g.Wp, 256, e->P);
+
+  // ---- replay: H V_i and the duals every iteration started from ----
+  LPC_RT(rt::memset_async(tape_hv(e, 0), 0, rb_bytes, e->stream));
+  for (int k = 0; k < 4; ++k) LPC_RT(rt::memset_async(tape_dual(e, k, 0), 0, rb_bytes, e->stream));
+  for (int i = 1; i <= n; ++i) LPC_OK(convolve_planar(e, tape_v(e, i), tape_hv(e, i), e->P, true, false));
+  for (int i = 0; i + 1 < n; ++i)
+    LPC_OK(launch_k(e, -1, k_admm_bwd_replay<256>, pw, 256, 0, g, bwd_scalars(e, i, n), (const real*)tape_v(e, i),
+                    (const real*)tape_hv(e, i), (const real*)tape_v(e, i + 1), (const real*)tape_hv(e, i + 1),
+                    (const real*)e->Y, (const real*)tape_dual(e, 0, i), (const real*)tape_dual(e, 1, i),
+                    (const real*)tape_dual(e, 2, i), (const real*)tape_dual(e, 3, i), tape_dual(e, 0, i + 1),
+                    tape_dual(e, 1, i + 1), tape_dual(e, 2, i + 1), tape_dual(e, 3, i + 1)));
+
+  // ---- the start: vb = pad(dL/dout [crop(V_n) > 0]), every other adjoint 0, so r_sp = vb and a = 0 ----
+  real *xib = tape_work(e, 0), *rhob = tape_work(e, 1);      // work 2 .. 5: etab0[0], etab1[0], etab0[1], etab1[1]
+  real *rbar = tape_work(e, 6), *hr = tape_work(e, 7), *gb = grad_data ? tape_work(e, 8) : nullptr;
+  LPC_RT(rt::memset_async(xib, 0, 4 * rb_bytes, e->stream));
+  LPC_RT(rt::memset_async(e->admm.Rsp, 0, rb_bytes, e->stream));
+  LPC_RT(rt::memset_async(e->admm.Aarr, 0, rb_bytes, e->stream));
+  LPC_OK(hwc_to_planar(e, grad_out, e->admm.Rsp + (long)g.sh * g.rpitch + g.sw, e->cfg.batch, g.H, g.W, g.rpitch, g.rplane));
+  LPC_OK(launch_k(e, -1, k_admm_bwd_seed<256>, grid1d((long)g.H * g.W, 256, e->P), 256, 0, g, (const real*)tape_v(e, n),
+                  e->admm.Rsp));
+
+  // ---- the sweep: one spectral step and one image-domain launch per iteration ----
+  const long tiles = bwd_tiles(g);
+  int cur = 0;
+  for (int i = n - 1; i >= 0; --i) {
+    const double par[4] = {e->admm.sched[0][i], e->admm.sched[1][i], e->admm.sched[2][i], e->admm.sched[3][i]};
+    LPC_OK(admm_spectral_plain(e, par, rbar, hr));
+    AdmmBwd a;
+    a.V = tape_v(e, i); a.V2 = tape_v(e, i + 1); a.HV = tape_hv(e, i); a.HV2 = tape_hv(e, i + 1);
+    a.xi = tape_dual(e, 0, i); a.eta0 = tape_dual(e, 1, i); a.eta1 = tape_dual(e, 2, i); a.rho = tape_dual(e, 3, i);
+    a.Y = e->Y; a.rb = rbar; a.hr = hr; a.xib = xib; a.rhob = rhob;
+    a.eb0 = tape_work(e, 2 + 2 * cur); a.eb1 = tape_work(e, 3 + 2 * cur);
+    a.eb0o = tape_work(e, 2 + 2 * (cur ^ 1)); a.eb1o = tape_work(e, 3 + 2 * (cur ^ 1));
+    a.gb = gb; a.Rsp = e->admm.Rsp; a.Aarr = e->admm.Aarr;
+    a.part = e->atape.part + (size_t)i * e->P * tiles * 4;
+    LPC_OK(launch_k(e, -1, k_admm_bwd_step<kBwdTH, kBwdQW>, dim3((unsigned)tiles, e->P, 1), kBwdTH * kBwdQW,
+                    admm_bwd_step_smem<kBwdTH, kBwdQW>(), g, bwd_scalars(e, i, n), a, (unsigned)bwd_tiles_x(g)));
+    cur ^= 1;
+    LPC_OK(launch_k(e, -1, k_admm_bwd_finish<256>, dim3(1), 256, admm_bwd_red_bytes<256>(), (const double*)a.part,
+                    (long)e->P * tiles, par[3] / (par[1] * par[1]), 1.0 / par[1], grad_mu1 + i, grad_mu2 + i, grad_mu3 + i,
+                    grad_tau + i));
+  }
+  if (grad_data)
+    LPC_OK(launch_k(e, -1, k_gd_bwd_gdata<256>, grid1d(g.uplane, 256, e->cfg.batch), 256, 0, (const real*)gb, grad_data,
+                    (long)g.uplane, e->cfg.channels, e->data_channels));
+  return 0;
+}

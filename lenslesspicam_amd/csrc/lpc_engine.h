@@ -18,6 +18,7 @@
 //                    kernels (the update rows in three units: half-length rows, paired rows without / with the folded
 //                    radix-2 stage)
 //   lpc_gd_bwd.cpp   reverse mode of unrolled FISTA: the fused row kernels of lpc_fista_backward
+//   lpc_admm_bwd.cpp reverse mode of unrolled ADMM: the tape of iterates, the replay and the sweep of lpc_admm_backward
 //   lpc_jit.cpp      plan modules: find / compile / load (lpc_plan.h)
 //   lpc_module.cpp   NOT part of the library: the source of a plan module (compile-time-plan kernels of one frame shape)
 #pragma once
@@ -160,6 +161,21 @@ struct AdmmState {
   // plug-and-play ADMM (lpc_admm_pnp_begin / _end): explicit state in the arrays the fused path uses for the TV duals
   //   eta0[0] = eta, eta1[0] = U, eta0[1] = X, eta1[1] = W   (all image-shaped)
   bool pnp_mode = false, pnp_pending = false;
+  bool custom_gram = false;    // lpc_set_psi_gram replaced the finite-difference gram (until the next lpc_set_psf)
+};
+
+// reverse mode of unrolled ADMM (lpc_admm_record / lpc_admm_backward; lpc_admm_bwd.cpp).  ONE allocation of 6 n + 11 padded
+// state arrays for a schedule of n iterations:
+//   V_0 .. V_n | H V_0 .. H V_n | xi_0 .. xi_{n-1} | eta0_i | eta1_i | rho_i | work: xib, rhob, etab0[0], etab1[0],
+//   etab0[1], etab1[1], rb, hr | g_b (un-padded planes inside a padded array's room)
+// The recorded forward writes V_i only; the backward's replay fills in the rest.  `part`: the partial sums of the four
+// reductions, 4 doubles per workgroup of k_admm_bwd_step and iteration.
+struct AdmmTape {
+  bool rec_on = false;
+  real* tape = nullptr;
+  double* part = nullptr;
+  int tape_n = 0;              // iterations the tape was allocated for
+  long tape_iters = -1;        // iterations recorded since the last reset (-1: nothing recorded)
 };
 
 // gradient-descent family: state (un-padded planes)
@@ -230,6 +246,7 @@ struct lpc_engine : LaunchCtx {
   AdmmState admm;
   GdState gd;
   FistaSchedule fista;
+  AdmmTape atape;
 };
 typedef lpc_engine Engine;
 
@@ -398,6 +415,14 @@ int admm_form_image(Engine* e, real* dev_out);
 int admm_get_state(Engine* e, const std::string& nm, real* dev_out);
 int admm_kernel_bytes(Engine* e, int kid, double* bytes);
 double admm_model_bytes(const Engine* e);
+int admm_spectral_plain(Engine* e, const double par[4], real* Vout, real* HVout);   // (Rsp, Aarr) -> S(Rsp + HT Aarr), H of it, with par's R_divmat
+// lpc_admm_bwd.cpp
+void admm_tape_free(Engine* e);
+int admm_tape_alloc(Engine* e);
+int admm_tape_reset(Engine* e);                    // admm_reset: V_0, or nothing when the handle does not record
+int admm_tape_push(Engine* e, const real* Vnew);   // admm_iterate: the iterate an iteration just wrote
+int admm_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_mu1, real* grad_mu2, real* grad_mu3,
+                  real* grad_tau);
 // lpc_gd_host.cpp
 int gd_alloc(Engine* e);
 int gd_setup_constants(Engine* e);

@@ -1,71 +1,218 @@
 """
-Unrolled ADMM *inference* on the MI355X engine: the camera-inversion stage of the reference's
-``UnrolledADMM`` (``lensless/recon/unrolled_admm.py:20-240``) -- per-iteration step sizes
-``mu1[i], mu2[i], mu3[i], tau[i]`` and batched measurements -- without the trainable parts
-(autograd, pre/post-processor networks: out of scope).
+Unrolled ADMM on the MI355X engine: the camera-inversion stage of the reference's ``UnrolledADMM``
+(``lensless/recon/unrolled_admm.py:20-240``, "LeADMM") -- per-iteration step sizes ``mu1[i], mu2[i], mu3[i], tau[i]``
+and batched measurements -- inference and training.
 
 The arithmetic is the ADMM kernels' own: the fused prox/update kernel takes the previous
 iteration's parameters for the pending dual updates and the current ones for the prox, and the
 spectral solve forms ``R_divmat[i]`` on the fly, so a schedule costs nothing per iteration.
+
+``UnrolledADMM`` is a ``torch.nn.Module`` like the reference's: ``_mu1_p, _mu2_p, _mu3_p, _tau_p`` (``n_iter`` float32
+values each) are ``nn.Parameter`` s on the PSF's device, under the reference's names and in its order, so ``state_dict()``
+round-trips with its checkpoints (``skip_unrolled=True`` keeps them plain tensors).  ``forward(batch)`` with autograd
+enabled and a parameter or ``batch`` requiring a gradient runs as one ``torch.autograd.Function``: the forward is the
+inference launch sequence with the handle keeping its iterates (``lpc_admm_record``), the backward a replay of the duals
+and one reverse sweep in fused HIP kernels (``lpc_admm_backward``, csrc/lpc_admm_bwd_kernels.h) plus the chain through
+``abs`` and the float32 cast on ``n_iter``-sized tensors.  There is one tape per solver: ``backward()`` after a later
+``forward()`` of the same object raises; a forward without gradients in between keeps the tape's memory
+(``release_tape()`` gives it back) and is the inference path, bit for bit.  The parameters require a gradient by default,
+so ANY ``forward()`` outside ``torch.no_grad()`` records: it allocates the tape, ``6 n + 11`` padded state arrays of the
+batch (include/lpc.h: ``lpc_admm_record``; 41 arrays for n = 5) -- run inference
+under ``no_grad`` or with ``skip_unrolled=True``.  What such a forward returns carries a graph; so that code which only
+wants the image (``out.cpu().numpy()``) keeps working, it is a ``torch.Tensor`` subclass (``_Estimate``) whose NumPy
+conversion detaches -- the subclass travels with every tensor derived from it, the loss included, and is a plain tensor in
+every other respect.  Not differentiated (``NotImplementedError``;
+from ``backward()`` for ``depth > 1``, frames whose padded height or width is odd and an initial estimate that asks for no
+gradient, so that their forward under autograd stays what it was -- it keeps no tape): the PSF (``psfs=`` or a PSF requiring a gradient),
+per-frame PSFs (a 5-D ``psfs``), the initial estimate, a custom ``psi`` and a denoiser.
+
+Pre- / post-processor networks are not taken by the constructor: the measurement gets a gradient, so compose them in
+torch around ``forward()``.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from .admm import ADMM
 
+_NAMES = ("_mu1_p", "_mu2_p", "_mu3_p", "_tau_p")
 
-class UnrolledADMM(ADMM):
+
+class _Estimate(torch.Tensor):
+    """What ``forward()`` returns under autograd.  The parameters require a gradient by default, so code that only wants
+    the image -- ``out.cpu().numpy()``, ``np.asarray(out)`` -- gets a tensor with a graph behind it where it used to get
+    a plain one; this one still converts to NumPy (of its detached values), and is an ordinary tensor otherwise."""
+
+    def numpy(self, *args, **kwargs):
+        return self.detach().as_subclass(torch.Tensor).numpy(*args, **kwargs)
+
+    def __array__(self, dtype=None, copy=None):
+        a = self.numpy()
+        return a if dtype is None else a.astype(dtype, copy=False)
+
+
+class _UnrolledADMMFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rec, batch, mu1_p, mu2_p, mu3_p, tau_p):
+        out = rec._run(batch, record=rec._backward_refusal() is None)
+        ctx.rec, ctx.gen = rec, rec._tape_gen
+        ctx.batch_meta = (tuple(batch.shape), batch.dtype, batch.device)
+        ctx.save_for_backward(mu1_p, mu2_p, mu3_p, tau_p)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        rec = ctx.rec
+        # (refused here, not in forward(): with the parameters requiring a gradient by default, a forward under autograd
+        # is what inference code written for the reference does as well; such a forward records nothing)
+        why = rec._backward_refusal()
+        if why is not None:
+            raise NotImplementedError("UnrolledADMM.backward: " + why)
+        if ctx.gen != rec._tape_gen:
+            raise RuntimeError("UnrolledADMM.backward: tape overwritten by a later forward() of the same solver")
+        n = rec._n_iter
+        need_b = ctx.needs_input_grad[1]
+        g = rec._to_dev(grad_out)
+        bshape = ctx.batch_meta[0]
+        g_data = rec._empty((bshape[0],) + bshape[2:]) if need_b else None
+        g_par = rec._empty((4, n))
+        rec._handle.admm_backward(g.data_ptr(), None if g_data is None else g_data.data_ptr(),
+                                  *(g_par[k].data_ptr() for k in range(4)), rec._stream())
+        # through |.| and the float32 cast, formed as _push_schedule forms them
+        grads = []
+        for k, p in enumerate(ctx.saved_tensors):
+            if not ctx.needs_input_grad[2 + k]:
+                grads.append(None)
+                continue
+            with torch.enable_grad():
+                q = p.detach().requires_grad_()
+                v = rec._schedule_of(q)
+                grads.append(torch.autograd.grad(v, q, g_par[k].to(device=v.device, dtype=v.dtype))[0])
+        gb = g_data[:, None].to(device=ctx.batch_meta[2], dtype=ctx.batch_meta[1]) if need_b else None
+        return (None, gb) + tuple(grads)
+
+
+class UnrolledADMM(ADMM, torch.nn.Module):
     def __init__(self, psf, dtype=None, n_iter=5, mu1=1e-6, mu2=1e-5, mu3=4e-5, tau=0.0001, psi=None,
-                 psi_adj=None, psi_gram=None, pad=False, norm="backward", **kwargs):
+                 psi_adj=None, psi_gram=None, pad=False, norm="backward", skip_unrolled=False, **kwargs):
         for key in ("pre_process", "post_process", "background_network", "psf_network", "compensation"):
             if kwargs.get(key) is not None:
-                raise NotImplementedError(f"{key}: learned components are outside the hot path (inference of the "
-                                          "unrolled iterations only)")
+                raise NotImplementedError(f"{key}: learned components are outside the hot path (compose them in torch "
+                                          "around forward(): the measurement gets a gradient)")
         assert isinstance(psf, torch.Tensor), "UnrolledADMM takes torch tensors, like the reference"
-        ones = torch.ones(n_iter, dtype=torch.float32)
-        # same attribute names as the reference so that checkpoints' state_dict entries can be assigned
-        self._mu1_p, self._mu2_p, self._mu3_p, self._tau_p = ones * mu1, ones * mu2, ones * mu3, ones * tau
+        torch.nn.Module.__init__(self)
         super().__init__(psf, dtype=dtype, mu1=mu1, mu2=mu2, mu3=mu3, tau=tau, psi=psi, psi_adj=psi_adj,
                          psi_gram=psi_gram, pad=pad, norm=norm, n_iter=n_iter, **kwargs)
+        self.skip_unrolled = skip_unrolled
+        # unrolled_admm.py:82-99: same attribute names as the reference so that checkpoints' state_dict entries can be
+        # assigned; parameters unless skip_unrolled
+        for name, val in zip(_NAMES, (mu1, mu2, mu3, tau)):
+            v = torch.ones(n_iter, dtype=torch.float32, device=psf.device) * val
+            setattr(self, name, v if skip_unrolled else torch.nn.Parameter(v))
+        self._tape_gen = 0
+        self._rec_state = (None, False)
+        self._push_schedule()
 
     def set_parameters(self, mu1=None, mu2=None, mu3=None, tau=None):
-        """Per-iteration values (length n_iter each), e.g. from a trained LeADMM checkpoint."""
-        for name, val in (("_mu1_p", mu1), ("_mu2_p", mu2), ("_mu3_p", mu3), ("_tau_p", tau)):
-            if val is not None:
-                v = torch.as_tensor(np.asarray(val, dtype=np.float32)).flatten()
-                assert v.numel() == self._n_iter, f"{name}: expected {self._n_iter} values"
-                setattr(self, name, v)
+        """Per-iteration values (length n_iter each), e.g. from a trained LeADMM checkpoint; copied in place."""
+        with torch.no_grad():
+            for name, val in zip(_NAMES, (mu1, mu2, mu3, tau)):
+                if val is not None:
+                    v = torch.as_tensor(np.asarray(val, dtype=np.float32)).flatten()
+                    assert v.numel() == self._n_iter, f"{name}: expected {self._n_iter} values"
+                    getattr(self, name).copy_(v)
 
     def load_state_dict(self, state, strict=False):
         """Accepts the unrolled parameters of a reference checkpoint; everything else is ignored."""
         self.set_parameters(**{k: state[f"_{k}_p"].detach().cpu().numpy()
                                for k in ("mu1", "mu2", "mu3", "tau") if f"_{k}_p" in state})
 
+    @staticmethod
+    def _schedule_of(p):
+        # unrolled_admm.py:140-144: the learnt values enter through torch.abs(), as float32
+        return torch.abs(p).to(torch.float32)
+
     def _push_schedule(self):
-        # unrolled_admm.py:147-151: the learnt values enter through torch.abs(), as float32
-        vals = [torch.abs(getattr(self, n)).to(torch.float32).cpu().numpy().astype(np.float64)
-                for n in ("_mu1_p", "_mu2_p", "_mu3_p", "_tau_p")]
+        """Hands the current values to the handle, at every reset: 4 n floats, read from the tensors themselves, so that
+        a write no version counter sees (``p.data.clamp_()``) is never missed."""
+        with torch.no_grad():
+            vals = [self._schedule_of(getattr(self, n)).cpu().numpy().astype(np.float64) for n in _NAMES]
         self._handle.set_admm_schedule(*vals)
 
     def reset(self, batch_size=None):
-        self._push_schedule()
+        if getattr(self, "_tau_p", None) is not None:      # (the base constructor resets before the parameters exist)
+            self._push_schedule()
         super().reset()
+
+    def _record(self, on):
+        """the handle keeps its iterates from the next reset on, or stops: a forward without gradients between two
+        training steps pauses the recording and keeps the tape's memory (no wait for the stream, no allocation)"""
+        state = (self._handle, bool(on))
+        if on or self._rec_state[0] is self._handle:      # (a handle that never recorded has nothing to pause)
+            if state != self._rec_state:
+                self._handle.admm_record(1 if on else -1)
+                self._rec_state = state
+
+    def release_tape(self):
+        """gives the tape's device memory back (it returns with the next forward that needs gradients)"""
+        if self._rec_state[0] is self._handle:
+            self._handle.admm_record(0)
+        self._rec_state = (None, False)
+        self._tape_gen += 1
+
+    def _run(self, batch, record=False):
+        self._data = batch
+        self._upload_data()
+        self._tape_gen += 1            # reset() starts the tape over: gradients of earlier forwards are gone
+        self._record(record)
+        self.reset()
+        self._iterate(self._n_iter)
+        return self._form_image()
+
+    def _backward_refusal(self):
+        """why ``backward()`` will refuse this solver, or None -- known before the forward runs, which then keeps no tape"""
+        if int(self._psf_shape[0]) > 1:
+            return "depth > 1 is not implemented"
+        if self._padded_shape[1] % 2 or self._padded_shape[2] % 2:
+            return (f"padded frame {self._padded_shape[1]} x {self._padded_shape[2]} has an odd length (the spectral step "
+                    "and the convolve / deconvolve pair are not self-adjoint there)")
+        if self._initial_est is not None:
+            return "training with an initial estimate is not implemented"
+        return None
+
+    def _refuse_gradients(self, batch, psfs):
+        """what lpc_admm_backward does not differentiate, refused before anything runs"""
+        if psfs is not None or (isinstance(self._psf, torch.Tensor) and self._psf.requires_grad):
+            raise NotImplementedError("UnrolledADMM: the gradient with respect to the PSF is not implemented")
+        if isinstance(self._initial_est, torch.Tensor) and self._initial_est.requires_grad:
+            raise NotImplementedError("UnrolledADMM: the gradient with respect to the initial estimate is not implemented")
+        if self._custom_psi is not None or self._pnp is not None:
+            raise NotImplementedError("UnrolledADMM: a custom psi and a denoiser are not differentiated")
 
     def forward(self, batch, psfs=None, background=None):
         """``batch``: (B, D=1, H, W, C) measurements -> (B, D, H, W, C) estimates after exactly
         ``n_iter`` unrolled iterations (trainable_recon.py:297-405 without the learned stages)."""
         assert isinstance(batch, torch.Tensor) and len(batch.shape) == 5, "batch must be of shape (N, D, H, W, C)"
-        if psfs is not None:
-            self._set_psf(psfs)
         if background is not None:
             raise NotImplementedError("background subtraction networks are outside the hot path")
-        self._data = batch
-        self._upload_data()
-        self.reset()
-        self._iterate(self._n_iter)
-        return self._form_image()
+        params = [getattr(self, n) for n in _NAMES]
+        psf_grad = (isinstance(psfs, torch.Tensor) and psfs.requires_grad) or \
+            (isinstance(self._psf, torch.Tensor) and self._psf.requires_grad)
+        init_grad = isinstance(self._initial_est, torch.Tensor) and self._initial_est.requires_grad
+        train = torch.is_grad_enabled() and (psf_grad or init_grad or any(t.requires_grad for t in [batch] + params))
+        if isinstance(psfs, torch.Tensor) and psfs.dim() == 5:
+            raise NotImplementedError("UnrolledADMM: per-frame PSFs (a 5-D psfs) are not implemented: one PSF for the "
+                                      "batch")
+        if train:
+            self._refuse_gradients(batch, psfs if psf_grad else None)
+        if psfs is not None:
+            self._set_psf(psfs)
+        if train:
+            return _UnrolledADMMFunction.apply(self, batch, *params).as_subclass(_Estimate)
+        return self._run(batch)
 
     def _form_image(self, out=None):
         # unrolled_admm.py:236-240 clips OUT of place (no state mutation): read the state directly

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """
-Times one training step of UnrolledFISTA on the MI355X: DiffuserCam-sized frames (270 x 480 x 3), B = 8, float32.
+Times one training step of UnrolledFISTA (or, with --algo admm, UnrolledADMM) on the MI355X: DiffuserCam-sized frames
+(270 x 480 x 3), B = 8, float32.
 
-    python tools/bench_unrolled_grad.py [--n 5 20] [--reps 30] [--package-root DIR] [--once] [--psf-grad]
+    python tools/bench_unrolled_grad.py [--algo fista|admm] [--n 5 20] [--reps 30] [--package-root DIR] [--once] [--psf-grad]
 
 Legs, each with warm-up and HIP events around every repetition (median, min, max in ms):
   (a) forward() under no_grad                       (--package-root: the same call on another checkout, e.g. the parent)
@@ -13,6 +14,10 @@ Legs, each with warm-up and HIP events around every repetition (median, min, max
   (e) backward() with the PSF gradient (its recorded forward is (b)'s)
   (f) torch.autograd over the restatement with the PSF as a leaf as well, forward + backward
 --once: one recorded forward + backward per n and nothing else (for a kernel trace; with --psf-grad: with the PSF gradient).
+--algo admm: legs (a) - (d) for UnrolledADMM (its restatement: the iteration of unrolled_admm.py:181-234 in torch.fft), plus
+  (g) a device-to-device copy of 16 padded state arrays: the copy rate the two new kernels are compared with
+and the algorithmic bytes one launch of k_admm_bwd_step / k_admm_bwd_replay moves (their times come from a kernel trace of
+a --once run).
 Prints one JSON line per n.
 """
 import argparse
@@ -30,6 +35,7 @@ def main():
     ap.add_argument("--package-root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--once", action="store_true")
     ap.add_argument("--psf-grad", action="store_true")
+    ap.add_argument("--algo", choices=["fista", "admm"], default="fista")
     args = ap.parse_args()
     sys.path.insert(0, args.package_root)
     import numpy as np
@@ -65,9 +71,11 @@ def main():
         ms.sort()
         return {"median": round(ms[len(ms) // 2], 4), "min": round(ms[0], 4), "max": round(ms[-1], 4)}
 
-    # the restatement: rfft2 of the padded frame, ifftshift + crop (RealFFTConvolve2D, pad=True, norm="ortho")
     Hp, Wp = 540, 960
     sh, sw = (Hp - H) // 2, (Wp - W) // 2
+    if args.algo == "admm":
+        return admm_legs(args, lpa, torch, timed, psf, data, w, (H, W, C, B, Hp, Wp, sh, sw))
+    # the restatement: rfft2 of the padded frame, ifftshift + crop (RealFFTConvolve2D, pad=True, norm="ortho")
     Hs = torch.fft.rfft2(torch.nn.functional.pad(psf, (0, 0, sw, Wp - W - sw, sh, Hp - H - sh)), norm="ortho", dim=(-3, -2))
 
     def spectrum(p):
@@ -141,6 +149,107 @@ def main():
                 res["e_over_c"] = round(res["e_backward_psf_ms"]["median"] / res["c_backward_ms"]["median"], 3)
                 be = res["b_recorded_forward_ms"]["median"] + res["e_backward_psf_ms"]["median"]
                 res["f_over_b_plus_e"] = round(res["f_torch_autograd_psf_fwd_bwd_ms"]["median"] / be, 3)
+        print(json.dumps(res), flush=True)
+
+
+def admm_legs(args, lpa, torch, timed, psf, data, w, geom):
+    H, W, C, B, Hp, Wp, sh, sw = geom
+    base = dict(mu1=1e-6, mu2=1e-4, mu3=4e-5, tau=2e-7)
+    names = ("mu1", "mu2", "mu3", "tau")
+    factors = dict(mu1=[1.0, 0.6, 1.5, 0.8, 2.0, 0.5], mu2=[0.7, 1.4, 2.0, 0.9, 0.55, 1.2],
+                   mu3=[1.8, 1.1, 0.5, 1.3, 0.75, 1.0], tau=[1.2, 1.7, 0.5, 0.9, 2.0, 0.65])
+    trainable = hasattr(lpa.UnrolledADMM, "release_tape")
+
+    def pad(v):
+        return torch.nn.functional.pad(v, (0, 0, sw, Wp - W - sw, sh, Hp - H - sh))
+
+    Hs = torch.fft.rfft2(pad(psf), dim=(-3, -2))
+    HH = (Hs.conj() * Hs).abs()
+    gram = torch.zeros((1, Hp, Wp, C), device=psf.device)
+    gram[0, 0, 0] = 4
+    gram[0, 0, 1] = gram[0, 0, -1] = gram[0, 1, 0] = gram[0, -1, 0] = -1
+    G = torch.fft.rfft2(gram, dim=(-3, -2)).abs()
+    mask = pad(torch.ones_like(psf))
+
+    def conv(x, adj):
+        X = torch.fft.rfft2(x, dim=(-3, -2)) * (Hs.conj() if adj else Hs)
+        return torch.fft.ifftshift(torch.fft.irfft2(X, dim=(-3, -2), s=(Hp, Wp)), dim=(-3, -2))
+
+    def psi(x):
+        return torch.stack((torch.roll(x, 1, dims=-3) - x, torch.roll(x, 1, dims=-2) - x), dim=x.dim())
+
+    def psi_t(u):
+        return (torch.roll(u[..., 0], -1, dims=-3) - u[..., 0]) + (torch.roll(u[..., 1], -1, dims=-2) - u[..., 1])
+
+    def restated(batch, ps, n):
+        m1, m2, m3, tau = (p.abs() for p in ps)
+        b = pad(batch)
+        v = torch.zeros((B, 1, Hp, Wp, C), device=psf.device)
+        hv, xi, rho = torch.zeros_like(v), torch.zeros_like(v), torch.zeros_like(v)
+        pv = torch.zeros(v.shape + (2,), device=psf.device)
+        eta = torch.zeros_like(pv)
+        for i in range(n):
+            s = pv + eta / m2[i]
+            U = torch.sign(s) * torch.clamp(s.abs() - tau[i] / m2[i], min=0)
+            X = (xi + m1[i] * hv + b) / (mask + m1[i])
+            Wv = torch.clamp(rho / m3[i] + v, min=0)
+            rk = (m3[i] * Wv - rho) + psi_t(m2[i] * U - eta) + conv(m1[i] * X - xi, True)
+            R = 1.0 / (m1[i] * HH + m2[i] * G + m3[i])
+            v = torch.fft.irfft2(R * torch.fft.rfft2(rk, dim=(-3, -2)), dim=(-3, -2), s=(Hp, Wp))
+            hv, pv = conv(v, False), psi(v)
+            xi = xi + m1[i] * (hv - X)
+            eta = eta + m2[i] * (pv - U)
+            rho = rho + m3[i] * (v - Wv)
+        return torch.clamp(v[..., sh:sh + H, sw:sw + W, :], min=0)
+
+    for n in args.n:
+        rec = lpa.UnrolledADMM(psf, n_iter=n, **base)
+        rec.set_parameters(**{k: [base[k] * factors[k][i % 6] for i in range(n)] for k in names})
+        batch = data.clone().requires_grad_(trainable)
+        if args.once:
+            (rec(batch) * w).sum().backward()
+            torch.cuda.synchronize()
+            continue
+        R, R0 = 4.0 * Hp * Wp * B * C, 4.0 * H * W * B * C
+        res = {"algo": "admm", "n_iter": n, "batch": B, "frame": [H, W, C], "package_root": args.package_root,
+               "plan": rec._handle.plan_info(),
+               # step: reads V_i, V_i+1, rb, hv, hv', hr, xi, rho, xib, rhob, eta (2), etab (2) + y; writes xib, rhob,
+               # etab (2), r_sp, a + g_b read and written.  replay: reads V, HV (2 each), xi, eta (2), rho + y; writes 4
+               "bytes_step": 20 * R + 3 * R0, "bytes_replay": 12 * R + R0}
+
+        def fwd_nograd():
+            with torch.no_grad():
+                rec(data)
+
+        res["a_forward_no_grad_ms"] = timed(fwd_nograd)
+        if trainable:
+            state = {}
+
+            def fwd():
+                state["loss"] = (rec(batch) * w).sum()
+
+            res["b_recorded_forward_ms"] = timed(fwd)
+            res["c_backward_ms"] = timed(lambda: state["loss"].backward(), setup=fwd)
+            ps = [getattr(rec, f"_{k}_p").detach().clone().requires_grad_() for k in names]
+            bt = data.clone().requires_grad_()
+            res["d_torch_autograd_fwd_bwd_ms"] = timed(lambda: (restated(bt, ps, n) * w).sum().backward())
+            src = torch.empty(int(8 * R / 4), dtype=torch.float32, device=psf.device)
+            dst = torch.empty_like(src)
+            res["g_copy_16R_ms"] = timed(lambda: dst.copy_(src))
+            res["copy_TBps"] = round(16 * R / res["g_copy_16R_ms"]["median"] * 1e-9, 3)
+            for p in ps + [bt, batch] + [getattr(rec, f"_{k}_p") for k in names]:
+                p.grad = None
+            (rec(batch) * w).sum().backward()
+            (restated(bt, ps, n) * w).sum().backward()
+            for k, p in zip(names, ps):
+                got = getattr(rec, f"_{k}_p").grad
+                res["check_rel_g_" + k] = float((got - p.grad).abs().max() / p.grad.abs().max())
+            res["check_rel_g_data"] = float((batch.grad - bt.grad).abs().max() / bt.grad.abs().max())
+            assert all(v < 1e-2 for k, v in res.items() if k.startswith("check_rel")), res   # the two paths time the same thing
+            bc = res["b_recorded_forward_ms"]["median"] + res["c_backward_ms"]["median"]
+            res["b_plus_c_ms"] = round(bc, 4)
+            res["c_over_a"] = round(res["c_backward_ms"]["median"] / res["a_forward_no_grad_ms"]["median"], 3)
+            res["d_over_b_plus_c"] = round(res["d_torch_autograd_fwd_bwd_ms"]["median"] / bc, 3)
         print(json.dumps(res), flush=True)
 
 
