@@ -256,6 +256,27 @@ int lpc_admm_backward(lpc_handle h, const lpc_real* dev_grad_out,   /* (B,D,H,W,
                       lpc_real* dev_grad_mu1, lpc_real* dev_grad_mu2, lpc_real* dev_grad_mu3,
                       lpc_real* dev_grad_tau,     /* n values each                                             */
                       void* stream);
+/* lpc_admm_backward_psf: lpc_admm_backward plus the gradient w.r.t. the PSF given to lpc_set_psf, summed over the batch.
+ * The PSF spectrum Hs enters iteration i three times: in H V_{i+1}, in HT a_i inside r_k (a_i = mu1[i] X_i - xi_i) and
+ * in R_i = 1 / (mu1[i] |Hs|^2 + mu2[i] |G| + mu3[i]).  With F = rfft2, phi the +-1 phase of the convolver's ifftshift,
+ * ab the adjoint of H V_{i+1} and rb the adjoint of r_k -- what the sweep holds in front of and behind the spectral step
+ * of iteration i -- and a_i recomputed from the tape, iteration i adds, summed over the frames of the batch,
+ *   g^ += phi conj(F V_{i+1}) F ab  +  phi conj(F rb) F a_i  -  2 mu1[i] Re(conj(F rb) F V_{i+1}) Hs
+ * in ONE complex accumulator of C spectrum planes kept across all iterations; after the sweep
+ *   g_psf = s * crop_to_the_PSF_window(irfft2(g^)),      s the norm factor of the PSF spectrum (1 for "backward"):
+ * one inverse transform.  Per iteration: one image-domain kernel (a_i), four forward transforms of P planes and one
+ * point-wise kernel over the spectra.  Same refusals (and messages) as lpc_admm_backward, and one more: a handle whose
+ * norm is not LPC_NORM_BACKWARD.  Deterministic, no atomics: a second call gives the same bits in all six outputs, and
+ * the other five are those of lpc_admm_backward.  Its workspace is allocated at the first call, counted in
+ * lpc_workspace_bytes, kept across a pause and freed with the tape by lpc_admm_record(h, 0):
+ *   (4 * P + C) * Hp * cpitch * 2 * sizeof(lpc_real)      bytes,
+ * P = B * C planes, cpitch = Wp / 2 + 1 rounded up to a multiple of 16 (Hp, Wp: lpc_padded_shape): the work spectra
+ * F V_{i+1}, F rb, F a_i, F ab and the accumulator.  lpc_admm_backward itself allocates and launches nothing of this.
+ * dev_grad_psf NULL: lpc_admm_backward. */
+int lpc_admm_backward_psf(lpc_handle h, const lpc_real* dev_grad_out, lpc_real* dev_grad_data, lpc_real* dev_grad_mu1,
+                          lpc_real* dev_grad_mu2, lpc_real* dev_grad_mu3, lpc_real* dev_grad_tau,
+                          lpc_real* dev_grad_psf,    /* (D,H,W,C): w.r.t. the PSF                                */
+                          void* stream);
 
 /* ---- the hot loop: `for i in range(n_iter): self._update(i)`  recon.py:575-576 ------ */
 /* exactly n_iter iterations, asynchronous on `stream`; no early exit exists on this path */

@@ -133,6 +133,7 @@ class Lib:
             "lpc_fista_backward_psf": [vp, fp, fp, fp, fp, fp, fp, vp],
             "lpc_admm_record": [vp, C.c_int],
             "lpc_admm_backward": [vp, fp, fp, fp, fp, fp, fp, vp],
+            "lpc_admm_backward_psf": [vp, fp, fp, fp, fp, fp, fp, fp, vp],
             "lpc_form_image": [vp, fp, vp],
             "lpc_get_state": [vp, C.c_char_p, fp, vp],
             "lpc_profile_enable": [vp, C.c_int],
@@ -302,6 +303,13 @@ class Handle:
         """replay + reverse sweep over the tape: device pointers; ``grad_data_ptr`` may be None (lpc_admm_backward)"""
         self._c(self.lib.dll.lpc_admm_backward(self.h, grad_out_ptr, grad_data_ptr, grad_mu1_ptr, grad_mu2_ptr,
                                                grad_mu3_ptr, grad_tau_ptr, stream))
+
+    def admm_backward_psf(self, grad_out_ptr, grad_data_ptr, grad_mu1_ptr, grad_mu2_ptr, grad_mu3_ptr, grad_tau_ptr,
+                          grad_psf_ptr, stream=0):
+        """``admm_backward`` plus the gradient w.r.t. the PSF, (D, H, W, C), summed over the batch; ``grad_psf_ptr`` None:
+        ``admm_backward`` (lpc_admm_backward_psf)"""
+        self._c(self.lib.dll.lpc_admm_backward_psf(self.h, grad_out_ptr, grad_data_ptr, grad_mu1_ptr, grad_mu2_ptr,
+                                                   grad_mu3_ptr, grad_tau_ptr, grad_psf_ptr, stream))
 
     def clear_admm_schedule(self):
         self._c(self.lib.dll.lpc_set_admm_schedule(self.h, 0, None, None, None, None))

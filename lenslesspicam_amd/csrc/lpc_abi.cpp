@@ -262,8 +262,8 @@ int lpc_admm_record(lpc_handle e, int on) {
   return e->admm.sched[0].empty() ? 0 : admm_tape_alloc(e);     // (no schedule yet: lpc_reset allocates)
 }
 
-int lpc_admm_backward(lpc_handle e, const real* dev_grad_out, real* dev_grad_data, real* dev_grad_mu1, real* dev_grad_mu2,
-                      real* dev_grad_mu3, real* dev_grad_tau, void* stream) {
+static int admm_backward_checked(lpc_handle e, const real* dev_grad_out, real* dev_grad_data, real* dev_grad_mu1,
+                                 real* dev_grad_mu2, real* dev_grad_mu3, real* dev_grad_tau, real* dev_grad_psf, void* stream) {
   if (!e || !dev_grad_out || !dev_grad_mu1 || !dev_grad_mu2 || !dev_grad_mu3 || !dev_grad_tau)
     return fail("lpc_admm_backward: null argument");
   if (e->cfg.algo != LPC_ALGO_ADMM) return fail("lpc_admm_backward: not an ADMM handle");
@@ -283,8 +283,21 @@ int lpc_admm_backward(lpc_handle e, const real* dev_grad_out, real* dev_grad_dat
     return fail("lpc_admm_backward: " + std::to_string(e->iters_done) + " iterations since the reset, the schedule has " +
                 std::to_string(n));
   if (dev_grad_data && !e->data_set) return fail("lpc_admm_backward: no data set");
+  if (dev_grad_psf && e->cfg.norm != LPC_NORM_BACKWARD)
+    return fail("lpc_admm_backward_psf: the gradient with respect to the PSF is implemented for norm \"backward\" only");
   e->stream = (lpcStream_t)stream;
-  return admm_backward(e, dev_grad_out, dev_grad_data, dev_grad_mu1, dev_grad_mu2, dev_grad_mu3, dev_grad_tau);
+  return admm_backward(e, dev_grad_out, dev_grad_data, dev_grad_mu1, dev_grad_mu2, dev_grad_mu3, dev_grad_tau, dev_grad_psf);
+}
+int lpc_admm_backward(lpc_handle e, const real* dev_grad_out, real* dev_grad_data, real* dev_grad_mu1, real* dev_grad_mu2,
+                      real* dev_grad_mu3, real* dev_grad_tau, void* stream) {
+  return admm_backward_checked(e, dev_grad_out, dev_grad_data, dev_grad_mu1, dev_grad_mu2, dev_grad_mu3, dev_grad_tau, nullptr,
+                               stream);
+}
+// ... and the gradient w.r.t. the PSF (dev_grad_psf null: lpc_admm_backward); same refusals, same messages, plus the norm's
+int lpc_admm_backward_psf(lpc_handle e, const real* dev_grad_out, real* dev_grad_data, real* dev_grad_mu1, real* dev_grad_mu2,
+                          real* dev_grad_mu3, real* dev_grad_tau, real* dev_grad_psf, void* stream) {
+  return admm_backward_checked(e, dev_grad_out, dev_grad_data, dev_grad_mu1, dev_grad_mu2, dev_grad_mu3, dev_grad_tau,
+                               dev_grad_psf, stream);
 }
 
 int lpc_iterate(lpc_handle e, int n_iter, void* stream) {

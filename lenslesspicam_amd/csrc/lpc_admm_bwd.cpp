@@ -11,6 +11,8 @@ static inline long bwd_tiles(const PlaneGeom& g) { return bwd_tiles_x(g) * ((g.H
 
 void admm_tape_free(Engine* e) {
   AdmmTape& t = e->atape;
+  dev_free(e, t.psf_ws);         // the PSF gradient's workspace goes with the tape
+  t.psf_ws = nullptr;
   if (!t.tape) return;
   dev_free(e, t.tape);
   dev_free(e, t.part);
@@ -75,12 +77,30 @@ static AdmmBwdScalars bwd_scalars(const Engine* e, int i, int n) {
   return p;
 }
 
+// full 2-D spectrum of P padded state arrays, in the PSF spectrum's own layout (the generic path of set_psf)
+static int psf_spectrum(Engine* e, const real* x, real2* S) {
+  LPC_OK(rows_fwd_single(e, src_padded(e, x), S, e->P, -1));
+  return cols_fwd_full(e, S, e->P, 0, e->g.Hp);
+}
+
+// grad_psf (lpc_admm_backward_psf; the terms: lpc_admm_bwd_kernels.h) adds per iteration i, in front of its spectral
+// step: a_i recomputed into `rbar` (free until that step writes it) and the full spectra of V_{i+1}, a_i and ab = Aarr
+// (which k_admm_bwd_step of the same i overwrites); behind it the spectrum of rb and ONE k_admm_bwd_psf_acc.  After the
+// sweep the accumulator goes through the convolution middle as the multiplier of a unit impulse's spectrum (= 1
+// everywhere: the inverse column passes of the accumulator, 1 / (Hp Wp) folded in) and the inverse rows with the crop to
+// the PSF window.  Without grad_psf nothing changes.
 int admm_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_mu1, real* grad_mu2, real* grad_mu3,
-                  real* grad_tau) {
+                  real* grad_tau, real* grad_psf) {
   const PlaneGeom& g = e->g;
   const int n = e->atape.tape_n;
   const size_t rb_bytes = (size_t)g.rplane * e->P * sizeof(real);
   const dim3 pw = grid1d((long)g.Hp * g.Wp, 256, e->P);
+  const size_t sp = (size_t)g.cplane * e->P;
+  real2 *FV = nullptr, *FR = nullptr, *FA = nullptr, *FB = nullptr, *acc = nullptr;
+  if (grad_psf) {
+    if (!e->atape.psf_ws) LPC_OK(dev_alloc(e, &e->atape.psf_ws, 4 * sp + (size_t)g.cplane * g.C));
+    FV = e->atape.psf_ws; FR = FV + sp; FA = FR + sp; FB = FA + sp; acc = FB + sp;
+  }
 
   // ---- replay: H V_i and the duals every iteration started from ----
   LPC_RT(rt::memset_async(tape_hv(e, 0), 0, rb_bytes, e->stream));
@@ -108,7 +128,21 @@ int admm_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_m
   int cur = 0;
   for (int i = n - 1; i >= 0; --i) {
     const double par[4] = {e->admm.sched[0][i], e->admm.sched[1][i], e->admm.sched[2][i], e->admm.sched[3][i]};
+    if (grad_psf) {
+      LPC_OK(launch_k(e, -1, k_admm_bwd_arec<256>, pw, 256, 0, g, bwd_scalars(e, i, n), (const real*)tape_hv(e, i),
+                      (const real*)tape_dual(e, 0, i), (const real*)e->Y, rbar));
+      LPC_OK(psf_spectrum(e, rbar, FA));
+      LPC_OK(psf_spectrum(e, tape_v(e, i + 1), FV));
+      LPC_OK(psf_spectrum(e, e->admm.Aarr, FB));
+    }
     LPC_OK(admm_spectral_plain(e, par, rbar, hr));
+    if (grad_psf) {
+      LPC_OK(psf_spectrum(e, rbar, FR));
+      LPC_OK(launch_k(e, -1, k_admm_bwd_psf_acc<256>, dim3((unsigned)((g.Wc + 255) / 256), (unsigned)g.Hp, (unsigned)g.C),
+                      256, 0, g, e->cfg.batch, (real)(2.0 * par[0]), (const real2*)FV, (const real2*)FR, (const real2*)FA,
+                      (const real2*)FB, (const real2*)e->Hs, (const real2*)e->phr, (const real2*)e->phc, acc,
+                      i == n - 1 ? 1 : 0));
+    }
     AdmmBwd a;
     a.V = tape_v(e, i); a.V2 = tape_v(e, i + 1); a.HV = tape_hv(e, i); a.HV2 = tape_hv(e, i + 1);
     a.xi = tape_dual(e, 0, i); a.eta0 = tape_dual(e, 1, i); a.eta1 = tape_dual(e, 2, i); a.rho = tape_dual(e, 3, i);
@@ -127,5 +161,16 @@ int admm_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_m
   if (grad_data)
     LPC_OK(launch_k(e, -1, k_gd_bwd_gdata<256>, grid1d(g.uplane, 256, e->cfg.batch), 256, 0, (const real*)gb, grad_data,
                     (long)g.uplane, e->cfg.channels, e->data_channels));
+  if (grad_psf) {
+    // rbar, hr are free again: one padded plane with a unit impulse at the origin, read as every channel's plane
+    LPC_RT(rt::memset_async(rbar, 0, (size_t)g.rplane * sizeof(real), e->stream));
+    LPC_OK(fill_planar(e, rbar, 1, (real)1.));
+    RealSrc unit = src_padded(e, rbar);
+    unit.plane_stride = 0;
+    LPC_OK(rows_fwd_single(e, unit, FV, g.C, -1));
+    LPC_OK(conv_middle(e, FV, g.C, false, 0, g.Hp, true, acc, g.C));
+    LPC_OK(rows_inv_single(e, FV, dst_cropped(e, hr), g.C, -1));
+    LPC_OK(planar_to_hwc(e, hr, grad_psf, 1, g.H, g.W, g.W, g.uplane, 0, 0, 0));
+  }
   return 0;
 }

@@ -283,6 +283,60 @@ __global__ __launch_bounds__(NT) void k_admm_bwd_seed(PlaneGeom g, const real* L
   }
 }
 
+// ---- the gradient w.r.t. the PSF (lpc_admm_backward_psf) -----------------------------------------------------------------
+// The PSF spectrum Hs enters iteration i in H V_{i+1} (the X half and the xi update of what follows), in HT a_i inside
+// r_k, and in R_i = 1 / (m1 |Hs|^2 + m2 |G| + m3).  With F = rfft2, phi the +-1 phase of the ifftshift (even padded
+// lengths; the engine's Hs does not carry it), ab the adjoint of H V_{i+1} (Aarr before the spectral step of iteration i),
+// rb what that step returns and a_i = m1 X_i - xi_i, iteration i adds, summed over the frames of the batch,
+//   g^ += phi conj(F V_{i+1}) F ab  +  phi conj(F rb) F a_i  -  2 m1 Re(conj(F rb) F V_{i+1}) Hs
+// and g_psf = s crop_to_the_PSF_window(irfft2(g^)).  The accumulator holds phi g^: the generic inverse rows apply the
+// ifftshift (a multiplication of the spectrum by phi) on the way out, so phi lands on the third term alone.
+
+// a_i = m1 X_i - xi_i, recomputed from the tape (X as in k_admm_bwd_step / k_admm_bwd_replay)
+template <int NT>
+__global__ __launch_bounds__(NT) void k_admm_bwd_arec(PlaneGeom g, AdmmBwdScalars p, const real* LPC_RESTRICT HV,
+                                                       const real* LPC_RESTRICT xi, const real* LPC_RESTRICT Y,
+                                                       real* LPC_RESTRICT a_o) {
+  const long n = (long)g.Hp * g.Wp;
+  const long pl = blockIdx.y;
+  const int dpl = (int)(pl / g.DC) * g.C + (int)(pl % g.C);
+  for (long e = (long)blockIdx.x * NT + threadIdx.x; e < n; e += (long)gridDim.x * NT) {
+    const int r = (int)(e / g.Wp), c = (int)(e - (long)r * g.Wp);
+    const long o = pl * g.rplane + (long)r * g.rpitch + c;
+    const bool inside = (r >= g.sh) && (r < g.sh + g.H) && (c >= g.sw) && (c < g.sw + g.W);
+    const real yv = inside ? Y[(long)dpl * g.uplane + (long)(r - g.sh) * g.W + (c - g.sw)] : (real)0.;
+    const real x = (inside ? p.m_in : p.m_out) * (xi[o] + p.m1 * HV[o] + yv);
+    a_o[o] = p.m1 * x - xi[o];
+  }
+}
+
+// One thread per spectral point (row blockIdx.y, column k) and channel (blockIdx.z): the B frames of the channel in a loop,
+// one read-modify-write of the accumulator (`first`: a write).  Point-wise in the spectra's own layout -- whatever row
+// order the launch plan keeps, Hs, the phase tables and the four work spectra share it.  No atomics.
+template <int NT>
+__global__ __launch_bounds__(NT) void k_admm_bwd_psf_acc(PlaneGeom g, int nframes, real two_m1,
+                                                          const real2* LPC_RESTRICT FV, const real2* LPC_RESTRICT FR,
+                                                          const real2* LPC_RESTRICT FA, const real2* LPC_RESTRICT FB,
+                                                          const real2* LPC_RESTRICT Hs, const real2* LPC_RESTRICT phr,
+                                                          const real2* LPC_RESTRICT phc, real2* LPC_RESTRICT acc,
+                                                          int first) {
+  const int k = (int)blockIdx.x * NT + (int)threadIdx.x;
+  if (k >= g.Wc) return;
+  const int row = blockIdx.y, c = blockIdx.z;
+  const long off = (long)row * g.cpitch + k;
+  const real2 h = Hs[(long)c * g.cplane + off];
+  const real w = -two_m1 * (phr[row].x * phc[k].x);      // phi is real: +-1
+  real2 s = first ? make_real2((real)0., (real)0.) : acc[(long)c * g.cplane + off];
+  for (int b = 0; b < nframes; ++b) {
+    const long o = (long)(b * g.C + c) * g.cplane + off;
+    const real2 v = FV[o], r = FR[o], a = FA[o], ab = FB[o];
+    const real t = w * (r.x * v.x + r.y * v.y);           // -2 m1 phi Re(conj(F rb) F V_{i+1})
+    s.x += (v.x * ab.x + v.y * ab.y) + (r.x * a.x + r.y * a.y) + t * h.x;
+    s.y += (v.x * ab.y - v.y * ab.x) + (r.x * a.y - r.y * a.x) + t * h.y;
+  }
+  acc[(long)c * g.cplane + off] = s;
+}
+
 // ---- the finishing sum of iteration i: block q adds quantity q of every workgroup in a fixed order ----------------------
 // g_mu1 = s0;  g_mu2 = s1 - s3 thr / m2;  g_mu3 = s2;  g_tau = s3 / m2        (thr = tau / m2)
 template <int NT>

@@ -176,6 +176,9 @@ struct AdmmTape {
   double* part = nullptr;
   int tape_n = 0;              // iterations the tape was allocated for
   long tape_iters = -1;        // iterations recorded since the last reset (-1: nothing recorded)
+  // PSF gradient (lpc_admm_backward_psf), allocated at its first call and freed with the tape: four work spectra of P
+  // planes (F V_{i+1}, F rb, F a_i, F ab) and the accumulator, C planes
+  real2* psf_ws = nullptr;
 };
 
 // gradient-descent family: state (un-padded planes)
@@ -422,7 +425,7 @@ int admm_tape_alloc(Engine* e);
 int admm_tape_reset(Engine* e);                    // admm_reset: V_0, or nothing when the handle does not record
 int admm_tape_push(Engine* e, const real* Vnew);   // admm_iterate: the iterate an iteration just wrote
 int admm_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_mu1, real* grad_mu2, real* grad_mu3,
-                  real* grad_tau);
+                  real* grad_tau, real* grad_psf = nullptr);
 // lpc_gd_host.cpp
 int gd_alloc(Engine* e);
 int gd_setup_constants(Engine* e);

@@ -23,11 +23,23 @@ wants the image (``out.cpu().numpy()``) keeps working, it is a ``torch.Tensor`` 
 conversion detaches -- the subclass travels with every tensor derived from it, the loss included, and is a plain tensor in
 every other respect.  Not differentiated (``NotImplementedError``;
 from ``backward()`` for ``depth > 1``, frames whose padded height or width is odd and an initial estimate that asks for no
-gradient, so that their forward under autograd stays what it was -- it keeps no tape): the PSF (``psfs=`` or a PSF requiring a gradient),
-per-frame PSFs (a 5-D ``psfs``), the initial estimate, a custom ``psi`` and a denoiser.
+gradient, so that their forward under autograd stays what it was -- it keeps no tape): the PSF unless the solver was
+built with ``psf_grad=True`` (``psfs=`` or a PSF requiring a gradient), per-frame PSFs (a 5-D ``psfs``), the initial
+estimate, a custom ``psi`` and a denoiser.
 
-Pre- / post-processor networks are not taken by the constructor: the measurement gets a gradient, so compose them in
-torch around ``forward()``.
+``UnrolledADMM(psf, ..., psf_grad=True)`` makes the PSF an autograd input as well: ``forward(batch, psfs=p)`` with
+``p.requires_grad``, or a ``p`` set earlier through ``_set_psf(p)``, gets ``dL/dp`` in ``p``'s shape, dtype and device,
+summed over the batch, from the same reverse sweep (``lpc_admm_backward_psf``: three cross terms per iteration -- through
+``H V``, through ``HT`` inside ``r_k`` and through ``R_divmat`` -- accumulated in ONE spectrum of C planes, one inverse
+transform at the end; the engine still works on its detached device copy of the PSF).  It costs a workspace of
+``4 P + C`` spectrum planes on top of the tape (include/lpc.h), allocated by the first backward that needs it and given
+back by ``release_tape()``.  When nothing of the PSF requires a gradient the backward is ``lpc_admm_backward``, bit for
+bit.  ``norm`` must be ``"backward"`` (the default) for this gradient; one PSF for the batch.  The default is
+``psf_grad=False``: every refusal above is unchanged.
+
+Pre- / post-processor networks are not taken by the constructor: the measurement (and with ``psf_grad=True`` the PSF)
+gets a gradient, so compose them in torch around ``forward()`` -- ``post(rec(pre(batch), psfs=psf + net(psf)))`` trains
+all of it.
 """
 from __future__ import annotations
 
@@ -55,8 +67,9 @@ class _Estimate(torch.Tensor):
 
 class _UnrolledADMMFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rec, batch, mu1_p, mu2_p, mu3_p, tau_p):
+    def forward(ctx, rec, batch, mu1_p, mu2_p, mu3_p, tau_p, psf=None):
         out = rec._run(batch, record=rec._backward_refusal() is None)
+        ctx.psf_meta = None if psf is None else (tuple(psf.shape), psf.dtype, psf.device)
         ctx.rec, ctx.gen = rec, rec._tape_gen
         ctx.batch_meta = (tuple(batch.shape), batch.dtype, batch.device)
         ctx.save_for_backward(mu1_p, mu2_p, mu3_p, tau_p)
@@ -75,12 +88,17 @@ class _UnrolledADMMFunction(torch.autograd.Function):
             raise RuntimeError("UnrolledADMM.backward: tape overwritten by a later forward() of the same solver")
         n = rec._n_iter
         need_b = ctx.needs_input_grad[1]
+        need_p = ctx.psf_meta is not None and ctx.needs_input_grad[6]
         g = rec._to_dev(grad_out)
         bshape = ctx.batch_meta[0]
         g_data = rec._empty((bshape[0],) + bshape[2:]) if need_b else None
         g_par = rec._empty((4, n))
-        rec._handle.admm_backward(g.data_ptr(), None if g_data is None else g_data.data_ptr(),
-                                  *(g_par[k].data_ptr() for k in range(4)), rec._stream())
+        ptrs = (g.data_ptr(), None if g_data is None else g_data.data_ptr()) + tuple(g_par[k].data_ptr() for k in range(4))
+        if need_p:
+            g_psf = rec._empty(tuple(int(v) for v in rec._psf_shape))
+            rec._handle.admm_backward_psf(*ptrs, g_psf.data_ptr(), rec._stream())
+        else:      # (nothing of the PSF asks for a gradient: the parameter-only sweep, its bits and its cost)
+            rec._handle.admm_backward(*ptrs, rec._stream())
         # through |.| and the float32 cast, formed as _push_schedule forms them
         grads = []
         for k, p in enumerate(ctx.saved_tensors):
@@ -92,12 +110,16 @@ class _UnrolledADMMFunction(torch.autograd.Function):
                 v = rec._schedule_of(q)
                 grads.append(torch.autograd.grad(v, q, g_par[k].to(device=v.device, dtype=v.dtype))[0])
         gb = g_data[:, None].to(device=ctx.batch_meta[2], dtype=ctx.batch_meta[1]) if need_b else None
-        return (None, gb) + tuple(grads)
+        gp = None
+        if need_p:
+            shape, dtype, device = ctx.psf_meta
+            gp = g_psf.reshape(shape).to(device=device, dtype=dtype)
+        return (None, gb) + tuple(grads) + (gp,)
 
 
 class UnrolledADMM(ADMM, torch.nn.Module):
     def __init__(self, psf, dtype=None, n_iter=5, mu1=1e-6, mu2=1e-5, mu3=4e-5, tau=0.0001, psi=None,
-                 psi_adj=None, psi_gram=None, pad=False, norm="backward", skip_unrolled=False, **kwargs):
+                 psi_adj=None, psi_gram=None, pad=False, norm="backward", skip_unrolled=False, psf_grad=False, **kwargs):
         for key in ("pre_process", "post_process", "background_network", "psf_network", "compensation"):
             if kwargs.get(key) is not None:
                 raise NotImplementedError(f"{key}: learned components are outside the hot path (compose them in torch "
@@ -107,6 +129,7 @@ class UnrolledADMM(ADMM, torch.nn.Module):
         super().__init__(psf, dtype=dtype, mu1=mu1, mu2=mu2, mu3=mu3, tau=tau, psi=psi, psi_adj=psi_adj,
                          psi_gram=psi_gram, pad=pad, norm=norm, n_iter=n_iter, **kwargs)
         self.skip_unrolled = skip_unrolled
+        self.psf_grad = bool(psf_grad)      # opt in: a PSF that requires a gradient is differentiated, not refused
         # unrolled_admm.py:82-99: same attribute names as the reference so that checkpoints' state_dict entries can be
         # assigned; parameters unless skip_unrolled
         for name, val in zip(_NAMES, (mu1, mu2, mu3, tau)):
@@ -186,7 +209,11 @@ class UnrolledADMM(ADMM, torch.nn.Module):
     def _refuse_gradients(self, batch, psfs):
         """what lpc_admm_backward does not differentiate, refused before anything runs"""
         if psfs is not None or (isinstance(self._psf, torch.Tensor) and self._psf.requires_grad):
-            raise NotImplementedError("UnrolledADMM: the gradient with respect to the PSF is not implemented")
+            if not self.psf_grad:
+                raise NotImplementedError("UnrolledADMM: the gradient with respect to the PSF is not implemented")
+            if self._norm != "backward":
+                raise NotImplementedError(f"UnrolledADMM: the gradient with respect to the PSF is implemented for "
+                                          f"norm=\"backward\" only (this solver has norm=\"{self._norm}\")")
         if isinstance(self._initial_est, torch.Tensor) and self._initial_est.requires_grad:
             raise NotImplementedError("UnrolledADMM: the gradient with respect to the initial estimate is not implemented")
         if self._custom_psi is not None or self._pnp is not None:
@@ -211,7 +238,8 @@ class UnrolledADMM(ADMM, torch.nn.Module):
         if psfs is not None:
             self._set_psf(psfs)
         if train:
-            return _UnrolledADMMFunction.apply(self, batch, *params).as_subclass(_Estimate)
+            psf = self._psf if self.psf_grad and isinstance(self._psf, torch.Tensor) and self._psf.requires_grad else None
+            return _UnrolledADMMFunction.apply(self, batch, *params, psf).as_subclass(_Estimate)
         return self._run(batch)
 
     def _form_image(self, out=None):

@@ -15,9 +15,10 @@ Legs, each with warm-up and HIP events around every repetition (median, min, max
   (f) torch.autograd over the restatement with the PSF as a leaf as well, forward + backward
 --once: one recorded forward + backward per n and nothing else (for a kernel trace; with --psf-grad: with the PSF gradient).
 --algo admm: legs (a) - (d) for UnrolledADMM (its restatement: the iteration of unrolled_admm.py:181-234 in torch.fft), plus
-  (g) a device-to-device copy of 16 padded state arrays: the copy rate the two new kernels are compared with
-and the algorithmic bytes one launch of k_admm_bwd_step / k_admm_bwd_replay moves (their times come from a kernel trace of
-a --once run).
+  (g) a device-to-device copy of 16 padded state arrays: the copy rate the kernels of the reverse mode are compared with
+and the algorithmic bytes one launch of k_admm_bwd_step / k_admm_bwd_replay / k_admm_bwd_psf_acc moves (their times come
+from a kernel trace of a --once run).  With --psf-grad (``UnrolledADMM(..., psf_grad=True)``, ``rec._set_psf(p)``) legs (e)
+and (f) as above; (b) - (d) are then measured on the same solver BEFORE the PSF becomes a leaf.
 Prints one JSON line per n.
 """
 import argparse
@@ -163,17 +164,12 @@ def admm_legs(args, lpa, torch, timed, psf, data, w, geom):
     def pad(v):
         return torch.nn.functional.pad(v, (0, 0, sw, Wp - W - sw, sh, Hp - H - sh))
 
-    Hs = torch.fft.rfft2(pad(psf), dim=(-3, -2))
-    HH = (Hs.conj() * Hs).abs()
+    psf_grad = args.psf_grad and trainable
     gram = torch.zeros((1, Hp, Wp, C), device=psf.device)
     gram[0, 0, 0] = 4
     gram[0, 0, 1] = gram[0, 0, -1] = gram[0, 1, 0] = gram[0, -1, 0] = -1
     G = torch.fft.rfft2(gram, dim=(-3, -2)).abs()
     mask = pad(torch.ones_like(psf))
-
-    def conv(x, adj):
-        X = torch.fft.rfft2(x, dim=(-3, -2)) * (Hs.conj() if adj else Hs)
-        return torch.fft.ifftshift(torch.fft.irfft2(X, dim=(-3, -2), s=(Hp, Wp)), dim=(-3, -2))
 
     def psi(x):
         return torch.stack((torch.roll(x, 1, dims=-3) - x, torch.roll(x, 1, dims=-2) - x), dim=x.dim())
@@ -181,8 +177,18 @@ def admm_legs(args, lpa, torch, timed, psf, data, w, geom):
     def psi_t(u):
         return (torch.roll(u[..., 0], -1, dims=-3) - u[..., 0]) + (torch.roll(u[..., 1], -1, dims=-2) - u[..., 1])
 
-    def restated(batch, ps, n):
-        m1, m2, m3, tau = (p.abs() for p in ps)
+    Hs0 = torch.fft.rfft2(pad(psf), dim=(-3, -2))
+    HH0 = (Hs0.conj() * Hs0).abs()
+
+    def restated(batch, ps, n, p=None):      # p: the PSF as a leaf (its spectrum is then part of the graph)
+        Hs = Hs0 if p is None else torch.fft.rfft2(pad(p), dim=(-3, -2))
+        HH = HH0 if p is None else (Hs.conj() * Hs).abs()
+
+        def conv(x, adj):
+            X = torch.fft.rfft2(x, dim=(-3, -2)) * (Hs.conj() if adj else Hs)
+            return torch.fft.ifftshift(torch.fft.irfft2(X, dim=(-3, -2), s=(Hp, Wp)), dim=(-3, -2))
+
+        m1, m2, m3, tau = (q.abs() for q in ps)
         b = pad(batch)
         v = torch.zeros((B, 1, Hp, Wp, C), device=psf.device)
         hv, xi, rho = torch.zeros_like(v), torch.zeros_like(v), torch.zeros_like(v)
@@ -203,10 +209,12 @@ def admm_legs(args, lpa, torch, timed, psf, data, w, geom):
         return torch.clamp(v[..., sh:sh + H, sw:sw + W, :], min=0)
 
     for n in args.n:
-        rec = lpa.UnrolledADMM(psf, n_iter=n, **base)
+        rec = lpa.UnrolledADMM(psf, n_iter=n, **base, **({"psf_grad": True} if psf_grad else {}))
         rec.set_parameters(**{k: [base[k] * factors[k][i % 6] for i in range(n)] for k in names})
         batch = data.clone().requires_grad_(trainable)
         if args.once:
+            if psf_grad:
+                rec._set_psf(psf.clone().requires_grad_())
             (rec(batch) * w).sum().backward()
             torch.cuda.synchronize()
             continue
@@ -215,7 +223,10 @@ def admm_legs(args, lpa, torch, timed, psf, data, w, geom):
                "plan": rec._handle.plan_info(),
                # step: reads V_i, V_i+1, rb, hv, hv', hr, xi, rho, xib, rhob, eta (2), etab (2) + y; writes xib, rhob,
                # etab (2), r_sp, a + g_b read and written.  replay: reads V, HV (2 each), xi, eta (2), rho + y; writes 4
-               "bytes_step": 20 * R + 3 * R0, "bytes_replay": 12 * R + R0}
+               "bytes_step": 20 * R + 3 * R0, "bytes_replay": 12 * R + R0,
+               # PSF-gradient accumulate: reads four work spectra of B C planes, the PSF spectrum and the accumulator (C
+               # planes each), writes the accumulator; complex64 half spectra of Hp x (Wp / 2 + 1) points
+               "bytes_psf_acc": 8.0 * Hp * (Wp // 2 + 1) * (4 * B * C + 3 * C)}
 
         def fwd_nograd():
             with torch.no_grad():
@@ -250,6 +261,20 @@ def admm_legs(args, lpa, torch, timed, psf, data, w, geom):
             res["b_plus_c_ms"] = round(bc, 4)
             res["c_over_a"] = round(res["c_backward_ms"]["median"] / res["a_forward_no_grad_ms"]["median"], 3)
             res["d_over_b_plus_c"] = round(res["d_torch_autograd_fwd_bwd_ms"]["median"] / bc, 3)
+            if psf_grad:
+                pe, pl = psf.clone().requires_grad_(), psf.clone().requires_grad_()
+                rec._set_psf(pe)
+                res["e_backward_psf_ms"] = timed(lambda: state["loss"].backward(), setup=fwd)
+                res["f_torch_autograd_psf_fwd_bwd_ms"] = timed(lambda: (restated(bt, ps, n, pl) * w).sum().backward())
+                pe.grad = pl.grad = None
+                (rec(batch) * w).sum().backward()
+                (restated(bt, ps, n, pl) * w).sum().backward()
+                res["check_rel_g_psf"] = float((pe.grad - pl.grad).abs().max() / pl.grad.abs().max())
+                assert res["check_rel_g_psf"] < 1e-2, res
+                res["e_over_c"] = round(res["e_backward_psf_ms"]["median"] / res["c_backward_ms"]["median"], 3)
+                be = res["b_recorded_forward_ms"]["median"] + res["e_backward_psf_ms"]["median"]
+                res["b_plus_e_ms"] = round(be, 4)
+                res["f_over_b_plus_e"] = round(res["f_torch_autograd_psf_fwd_bwd_ms"]["median"] / be, 3)
         print(json.dumps(res), flush=True)
 
 
