@@ -102,6 +102,11 @@ typedef struct lpc_config {
  *                      (default 1: precombined once per PSF and step sizes into one 16-byte + one 4-byte load per element)
  *   k1_half=0          duals stored plain between the iterations of one call (default 1: half-applied, the tiled kernel
  *                      then does not read V_old: 9R -> 8R)
+ *   rho_rsp=0          ... rho~ stored and read between the iterations of one call (default 1: the tiled kernel recovers it
+ *                      from the r_sp it overwrites and the eta~ it loads anyway: 8R -> 7R; not on the three-launch plan)
+ *   xi_half=0          ... xi stored plain between the iterations of one call (default 1: half-applied, xi~ = -a, the X
+ *                      half of the forward rows then does not read H V_old inside the sensor window: 3 Rw -> 2 Rw)
+ *                      (k1_half=0 switches both off)
  *   k1_rows=0          keep the tiled TV / W kernel (default 1: paired rows of one or two quads per lane -- padded widths up
  *                      to 2048 -- take that half of the image-domain work as well: three launches per iteration, r_sp never
  *                      stored; rows of up to 1024 points then run on 256 lanes at every batch size)

@@ -452,6 +452,9 @@ int lpc_plan_info(lpc_handle e, char* buf, size_t n) {
          : pl.k1 == ADMM_K1_TV_W ? "; tiled TV / W kernel + X half inside the forward rows" : "; stand-alone image-domain kernel";
     if (pl.xi_window) s += pl.hv_skip ? " (xi inside the sensor window only, H V row transforms skipped outside it)"
                                       : " (xi inside the sensor window only)";
+    if (pl.rho_rsp || pl.xi_half)
+      s += std::string("; inside a call: ") + (pl.rho_rsp ? "rho read back from r_sp" : "") +
+           (pl.rho_rsp && pl.xi_half ? ", " : "") + (pl.xi_half ? "xi half-applied" : "");
   }
   if (e->cfg.algo == LPC_ALGO_ADMM && e->admm.g_sep) s += "; gram as row + column terms";
   if (e->cfg.algo == LPC_ALGO_FISTA)      // lpc_fista_backward (lpc_gd_bwd.cpp: gd_bwd_rows)

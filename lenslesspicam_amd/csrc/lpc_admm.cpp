@@ -36,6 +36,7 @@ static AdmmScalars admm_scalars(const Engine* e, const double cur[4]) {
   p.skipa = p.skiphv = 0;      // set by admm_iterate inside a call (AdmmScalars::skipa)
   p.rev = e->plan.rev_k1 ? 1 : 0;
   p.half_in = p.half_out = 0;  // set by admm_iterate between the iterations of one call (AdmmScalars::half_in)
+  p.rho_rsp = p.xi_in = p.xi_out = 0;      // likewise (AdmmScalars::rho_rsp, xi_in)
   return p;
 }
 
@@ -191,6 +192,11 @@ int admm_iterate(Engine* e, int n_iter) {
     // duals, the last one writes them -- nothing outside this loop sees the other form
     sc.half_in = (pl.k1_half && it > 0) ? 1 : 0;
     sc.half_out = (pl.k1_half && it + 1 < n_iter) ? 1 : 0;
+    // ... and under the same conditions rho~ is read back from r_sp and xi travels as -a inside the window
+    // (LaunchPlan::rho_rsp, xi_half): both neighbours of the boundary are iterations of this call
+    sc.rho_rsp = (pl.rho_rsp && sc.half_in) ? 1 : 0;
+    sc.xi_in = (pl.xi_half && it > 0) ? 1 : 0;
+    sc.xi_out = (pl.xi_half && it + 1 < n_iter) ? 1 : 0;
     // ADMM_K1_ROWS: the forward rows take the TV / W half as well -- same buffers, same ping-pong
     AdmmState& a = e->admm;
     const K1Rows k1 = {Vc, Vo, a.eta0[a.ecur], a.eta1[a.ecur], a.eta0[a.ecur ^ 1], a.eta1[a.ecur ^ 1], a.rho, pl.k1_xcd_order};
@@ -377,6 +383,7 @@ int admm_kernel_bytes(Engine* e, int kid, double* bytes) {
   const double Sc = 2 * eb * g.Hp * g.Wc * e->Ppsf;   // spectral constants
   const bool split = pl.N1 > 1, k1_rows = pl.k1 == ADMM_K1_ROWS;
   const double fr = (double)g.H / (double)g.Hp;
+  const double nxw = pl.xi_half ? 2.0 : 3.0;          // arrays the X half moves where xi lives: xi in, xi out (+ H V_old)
   double b = 0.0;
   switch (kid) {
     // SURVEY 8(d) figure for the stand-alone kernel (reads 8R+R0, writes 7R; the kernel itself moves 14R + R0: X is
@@ -386,16 +393,18 @@ int admm_kernel_bytes(Engine* e, int kid, double* bytes) {
     // rho and writes eta0, eta1, rho, r_sp = 9R (SURVEY's 15R + R0 minus its X part: reads HV, X, xi, y, writes xi, X,
     // a); the row kernel reads r_sp (R) and xi, HV, HV_old, y (3R + R0), writes xi (R) and the two spectra (2S).
     // ... and without V_old once the duals travel half-applied between the iterations of a call (k1_half): 8R
+    // ... and without rho in either direction once rho~ is recovered from r_sp, read in place of it (rho_rsp): 7R
     // ... k1_rows (small frames): not launched; the forward rows read V, eta0, eta1, rho (+ V_old without k1_half)
     // instead of r_sp and write eta0, eta1, rho: + 6R (7R)
-    case LPC_K_SPATIAL: b = k1_rows ? 0.0 : pl.xhalf_rows ? (pl.k1_half ? 8.0 : 9.0) * R : 15.0 * R + R0; break;
+    case LPC_K_SPATIAL: b = k1_rows ? 0.0 : pl.xhalf_rows ? (pl.rho_rsp ? 7.0 : pl.k1_half ? 8.0 : 9.0) * R : 15.0 * R + R0; break;
     // ... with xi confined to the sensor window (AdmmScalars::xiw) the row kernel reads r_sp, HV everywhere (2R) and
     // xi, HV_old / writes xi only over the window (3 window-sized arrays per plane) and y: 2R + 3 Rw + R0 + 2S
     // ... and with the H V row transforms skipped on rows wholly outside the window (AdmmScalars::skipa, steady state
     // of a long call; fr = H / Hp): rows fwd (1 + fr) R + 3 Rw + R0 + (1 + fr) S, rows inv (1 + fr) (S + R)
-    case LPC_K_ROW_FWD: b = (pl.hv_skip ? (1.0 + fr) * R + 3.0 * eb * g.H * g.W * e->P + R0 + (1.0 + fr) * S
-                                : pl.xi_window ? 2.0 * R + 3.0 * eb * g.H * g.W * e->P + R0 + 2.0 * S
-                                : pl.xhalf_rows ? 5.0 * R + R0 + 2.0 * S : 2.0 * R + 2.0 * S)
+    // ... and with xi half-applied between the iterations of a call (xi_half) H V_old is not read where xi is: 2 Rw
+    case LPC_K_ROW_FWD: b = (pl.hv_skip ? (1.0 + fr) * R + nxw * eb * g.H * g.W * e->P + R0 + (1.0 + fr) * S
+                                : pl.xi_window ? 2.0 * R + nxw * eb * g.H * g.W * e->P + R0 + 2.0 * S
+                                : pl.xhalf_rows ? (2.0 + nxw) * R + R0 + 2.0 * S : 2.0 * R + 2.0 * S)
                                + (k1_rows ? (pl.k1_half ? 6.0 : 7.0) * R : 0.0); break;
     case LPC_K_COL_A_FWD: b = split ? 4.0 * S : 0.0; break;
     case LPC_K_COL_MID: b = 4.0 * S + Sc + (e->admm.g_sep ? 0. : eb * g.Hp * g.Wc); break;  // + H (complex) + |G| (real, one plane; two vectors when it separates)

@@ -112,6 +112,8 @@ struct LaunchPlan {
   bool hv_skip = false;    // ... and rows wholly outside it skip the H V row transforms in both directions (AdmmScalars::skipa)
   AdmmK1 k1 = ADMM_K1_SCALAR;
   bool k1_half = false;    // duals half-applied between the iterations of one call (AdmmScalars::half_in)
+  bool rho_rsp = false;    // ... rho~ recovered from r_sp by the tiled TV / W kernel: rho not moved inside a call (AdmmScalars::rho_rsp)
+  bool xi_half = false;    // ... xi half-applied too: the X half does not read H V_old where xi lives (AdmmScalars::xi_in)
   int k1_xcd_order = 0;    // K1Rows::xcd_order
   AdmmMid admm_mid = ADMM_MID_RT_LDS;
   int conv_mid_reg = 0;    // convolution middle (conv_middle) in registers: its pass-B length; 0: in LDS

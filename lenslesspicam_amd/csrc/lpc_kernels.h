@@ -1302,6 +1302,20 @@ struct AdmmScalars {
   // plug-and-play, a caller's psi) sees the state of round 3.  Rounding differs from the reference's order of operations
   // by one ulp of the dual per iteration (float64 build: identical to 1e-16).
   int half_in, half_out;
+  // Two arrays that travel between the iterations of a call are exact functions of others that travel anyway:
+  // rho_rsp (k_admm_spatial_v4<.., HIN = true>, option rho_rsp): the previous iteration stored, in one statement,
+  //   rho~ = rho' - mu3 W   and   r_sp = (mu3 W - rho') + D(q),  D(q) = (q0[below] - q0) + (q1[right] - q1),  eta~ = -q,
+  // so rho~ = D(-eta~) - r_sp: the kernel loads its own pixel of r_sp where it would load rho~, forms D from the four
+  // stored eta~ values it loads anyway (same association as d1 + d2) and overwrites that r_sp in place; rho is neither
+  // written nor read between the iterations of a call (8 R -> 7 R), the last iteration writes the plain dual as before.
+  // (The FIRST iteration of a call runs the non-HIN kernel, which still writes a rho~ that nobody reads: one launch per call.)
+  // One rounding of r_sp's magnitude per iteration (float64 build: identical to 1e-15).
+  int rho_rsp;
+  // xi_in / xi_out (X half of the forward rows, option xi_half): inside the window xi travels half-applied as well,
+  //   xi~ = xi' - mu1 X = -a   (stored by an iteration with xi_out),   xi'' = xi~ + mu1p HV_new   (read with xi_in)
+  // -- the previous X need not be recomputed, so H V_old is not read inside the window (3 Rw -> 2 Rw).  Outside the
+  // window nothing changes (xi is not stored there inside a call; xi_store on the last iteration still reads H V_old).
+  int xi_in, xi_out;
 };
 // the estimate as the W-update saw it
 static __device__ __forceinline__ real w_sees(real v, bool clamped, bool inside) {
@@ -1551,7 +1565,8 @@ __global__ __launch_bounds__(NT) void k_admm_spatial_v4(PlaneGeom g, AdmmScalars
     const long o_rt = poff + (long)gr * g.rpitch + wrap_c(gc + 4);        // eta1 of the pixel right of the quad
     // global loads first (all independent)
     const real4 z4 = make_real4((real)0., (real)0., (real)0., (real)0.);
-    const real4 hv4 = XHALF ? ld4(HV + o) : z4, xi4 = XHALF ? ld4(xi + o) : z4, rho4 = ld4(rho + o);
+    const bool rsp_in = HIN && p.rho_rsp;      // rho~ recovered from this pixel's r_sp (AdmmScalars::rho_rsp)
+    const real4 hv4 = XHALF ? ld4(HV + o) : z4, xi4 = XHALF ? ld4(xi + o) : z4, rho4 = ld4((rsp_in ? Rsp : rho) + o);
     const real4 e04 = ld4(eta0 + o), e14 = ld4(eta1 + o), e0d4 = ld4(eta0 + o_dn);
     const real e1r = eta1[o_rt];
     real4 ho4 = z4;
@@ -1597,6 +1612,8 @@ __global__ __launch_bounds__(NT) void k_admm_spatial_v4(PlaneGeom g, AdmmScalars
           xiv = xiv + p.mu1p * (hv - xo);
         }
         if (HIN || p.half_in) {
+          // rhov holds r_sp_old: rho~ = (d1 + d2)_old - r_sp_old with q_old = -eta~ (AdmmScalars::rho_rsp)
+          if (rsp_in) rhov = ((e0s[i] - e0ds[i]) + (e1s[i] - e1s[i + 1])) - rhov;
           rhov = rhov + p.mu3p * vc;                // stored: rho - mu3p W_old (AdmmScalars::half_in)
         } else {
           const real wo = rmax(div_by(rhov, p.mu3p, p.r_mu3p) + w_sees(ocs[i + 1], p.clamp_old, inside), (real)0.);
@@ -1612,7 +1629,7 @@ __global__ __launch_bounds__(NT) void k_admm_spatial_v4(PlaneGeom g, AdmmScalars
       as[i] = p.mu1 * xnew - xiv;
     }
     if (XHALF) st4(xi + o, make_real4(xin[0], xin[1], xin[2], xin[3]));
-    st4(rho + o, make_real4(rhn[0], rhn[1], rhn[2], rhn[3]));
+    if (!(rsp_in && p.half_out)) st4(rho + o, make_real4(rhn[0], rhn[1], rhn[2], rhn[3]));   // (the next iteration reads r_sp instead)
     st4(eta0_out + o, make_real4(e0n[0], e0n[1], e0n[2], e0n[3]));
     st4(eta1_out + o, make_real4(e1n[0], e1n[1], e1n[2], e1n[3]));
     st4(Rsp + o, make_real4(rs[0], rs[1], rs[2], rs[3]));
@@ -1636,7 +1653,11 @@ static __device__ __forceinline__ XQuad xhalf_load(const PlaneGeom& g, const Adm
   c.hv = ld4(HV + o_row + gc);
   c.xi = c.ho = make_real4((real)0., (real)0., (real)0., (real)0.);
   if (!c.skip) c.xi = ld4(xi + o_row + gc);
-  if (!p.first && (!c.skip || p.xi_store)) c.ho = ld4(HVold + o_row + gc);
+  // H V_old: to recompute the previous X inside the window -- not with xi half-applied (AdmmScalars::xi_in) -- and for
+  // xi = mu1p (HV - HV_old) outside it when that is stored (xi_store: the last iteration of a call; that launch loads it
+  // for every quad, those wholly inside the window included, where nothing reads it -- deliberate: one launch per call, the
+  // parent form's traffic, no test per quad in the other ninety-nine)
+  if (!p.first && (p.xi_in ? (p.xiw && p.xi_store) : (!c.skip || p.xi_store))) c.ho = ld4(HVold + o_row + gc);
 #pragma unroll
   for (int i = 0; i < 4; ++i) { c.ys[i] = (real)0.; c.ins[i] = false; }
   if (row_in) {
@@ -1657,26 +1678,37 @@ static __device__ __forceinline__ XQuad xhalf_load(const PlaneGeom& g, const Adm
   }
   return c;
 }
-// xin: the updated xi (stored by the caller unless c.skip && !p.xi_store); as: a = mu1 X - xi'
+// xin: the updated xi -- half-applied, -a, with p.xi_out -- (stored by the caller unless c.skip && !p.xi_store);
+// as: a = mu1 X - xi'
 static __device__ __forceinline__ void xhalf_apply(const AdmmScalars& p, const XQuad& c, real xin[4], real as[4]) {
   const real hvs[4] = {c.hv.x, c.hv.y, c.hv.z, c.hv.w}, xis[4] = {c.xi.x, c.xi.y, c.xi.z, c.xi.w};
   const real hos[4] = {c.ho.x, c.ho.y, c.ho.z, c.ho.w};
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    real xiv = xis[i];
+    real xiv = xis[i], a;
     const real hv = hvs[i], yv = c.ys[i];
-    if (p.xiw && !c.ins[i]) {      // outside the window: a = mu1 HV, xi = mu1p (HV - HV_old) (stored on request only)
-      xin[i] = p.first ? (real)0. : p.mu1p * (hv - hos[i]);
-      as[i] = p.mu1 * hv;
-      continue;
+    // outside the window: a = mu1 HV, xi = mu1p (HV - HV_old) -- stored on request only (xi_store).  In a quad that
+    // straddles the window's edge these lanes are stored with the quad in every iteration, and with xi_in H V_old is not
+    // loaded (hos = 0): between the iterations of a call they hold GARBAGE.  Nothing reads them (this branch never reads
+    // xi) until the last iteration, which loads H V_old and rewrites them.
+    if (p.xiw && !c.ins[i]) {
+      xiv = p.first ? (real)0. : p.mu1p * (hv - hos[i]);
+      a = p.mu1 * hv;
+    } else {
+      if (!p.first) {
+        if (p.xi_in) {
+          xiv = xiv + p.mu1p * hv;                   // stored: xi' - mu1p X_old (AdmmScalars::xi_in)
+        } else {
+          const real xo = (c.ins[i] ? p.m_in_p : p.m_out_p) * (xiv + p.mu1p * hos[i] + yv);   // previous X
+          xiv = xiv + p.mu1p * (hv - xo);
+        }
+      }
+      const real xnew = (c.ins[i] ? p.m_in : p.m_out) * (xiv + p.mu1 * hv + yv);
+      a = p.mu1 * xnew - xiv;
+      if (p.xi_out) xiv = -a;
     }
-    if (!p.first) {
-      const real xo = (c.ins[i] ? p.m_in_p : p.m_out_p) * (xiv + p.mu1p * hos[i] + yv);   // previous X
-      xiv = xiv + p.mu1p * (hv - xo);
-    }
-    const real xnew = (c.ins[i] ? p.m_in : p.m_out) * (xiv + p.mu1 * hv + yv);
     xin[i] = xiv;
-    as[i] = p.mu1 * xnew - xiv;
+    as[i] = a;
   }
 }
 

@@ -141,6 +141,8 @@ struct EngineOpts {
   int mid_pc = 1;             // sequential middle on pair-line spectra: H, |G| and the phases precombined per (PSF, step sizes)
                               // into one 16-byte + one 4-byte load per element (PlanSpec::mid_pc); 0: loaded and combined per element
   int k1_half = 1;            // duals half-applied between the iterations of one call: the tiled kernel does not read V_old
+  int rho_rsp = 1;            // ... and reads rho~ back out of r_sp: rho is not moved between the iterations of a call
+  int xi_half = 1;            // ... xi half-applied as well: the X half of the forward rows does not read H V_old inside the window
   // -- block orders (permutations: results unchanged)
   int rev_order = 9;          // bit 0 / 1 / 2 / 3: the tiled ADMM kernel / forward pass A / inverse pass A / the LDS middle walk
                               // their grids BACKWARDS: a kernel that starts where its predecessor finished finds the last
@@ -203,6 +205,8 @@ static inline std::string parse_engine_opts(const char* str, EngineOpts& o) {
       else if (k == "k1_rows") o.k1_rows = (int)iv;
       else if (k == "k1_group") o.k1_group = (int)iv;
       else if (k == "k1_half") o.k1_half = (int)iv;
+      else if (k == "rho_rsp") o.rho_rsp = (int)iv;
+      else if (k == "xi_half") o.xi_half = (int)iv;
       else if (k == "mid_pc") o.mid_pc = (int)iv;
       else if (k == "rev_order") o.rev_order = (int)iv;
       else if (k == "gd_rev") o.gd_rev = (int)iv;

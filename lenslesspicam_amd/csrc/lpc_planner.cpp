@@ -333,6 +333,11 @@ void finish_plan(const lpc_config& c, const EngineOpts& o, const PlaneGeom& g, i
   pl.k1 = k1_rows ? ADMM_K1_ROWS : pl.xhalf_rows ? ADMM_K1_TV_W : g.Wp % 4 == 0 ? ADMM_K1_TILED : ADMM_K1_SCALAR;
   // duals half-applied between the iterations of one call (option k1_half=0: never)
   pl.k1_half = pl.xhalf_rows && o.k1_half != 0;
+  // ... then two of the arrays that travel are functions of the others: the tiled TV / W kernel reads rho~ back out of
+  // the r_sp it overwrites (the three-launch plan stores no r_sp), and the X half keeps xi as -a (options rho_rsp=0,
+  // xi_half=0: off; k1_half=0 implies both off)
+  pl.rho_rsp = pl.k1_half && pl.k1 == ADMM_K1_TV_W && o.rho_rsp != 0;
+  pl.xi_half = pl.k1_half && o.xi_half != 0;
   // K1Rows::xcd_order.  (The XCD-aware block orders assume the MI355X's 8 XCDs x 32 CUs and its dispatch rule "workgroup w
   // on XCD w % 8"; any other part gets launch order: the orders are permutations, results are the same.)
   pl.k1_xcd_order = cu != 256 ? 0 : (long)paired_rows_grid(g, false) * P <= 8192 ? -1 : std::max(0, o.k1_group);
