@@ -142,8 +142,8 @@ int lpc_set_data(lpc_handle e, const real* dev_data, int data_channels, void* st
   LPC_OK(hwc_to_planar(e, dev_data, e->Y, e->cfg.batch, g.H, g.W, g.W, g.uplane, data_channels));
   e->data_set = true;
   e->data_channels = data_channels;
-  e->fista.tape_iters = -1;      // a tape recorded with other data no longer matches (lpc_fista_backward refuses)
-  e->atape.tape_iters = -1;      // ... and lpc_admm_backward
+  e->fista_tape.invalidate();      // a tape recorded with other data no longer matches (lpc_fista_backward refuses)
+  e->admm_tape.invalidate();       // ... and lpc_admm_backward
   return 0;
 }
 
@@ -193,7 +193,7 @@ int lpc_set_admm_schedule(lpc_handle e, int n, const double* mu1, const double* 
   if (!e) return fail("null handle");
   if (e->cfg.algo != LPC_ALGO_ADMM) return fail("lpc_set_admm_schedule: not an ADMM handle");
   for (auto& v : e->admm.sched) v.clear();
-  e->atape.tape_iters = -1;      // a tape recorded with another schedule no longer matches (lpc_admm_backward refuses)
+  e->admm_tape.invalidate();      // a tape recorded with another schedule no longer matches (lpc_admm_backward refuses)
   if (n <= 0) return 0;
   if (!mu1 || !mu2 || !mu3 || !tau) return fail("lpc_set_admm_schedule: null array");
   for (int i = 0; i < n; ++i) {
@@ -214,11 +214,18 @@ int lpc_set_fista_schedule(lpc_handle e, int n, const real* alpha, const real* c
 int lpc_fista_record(lpc_handle e, int on) {
   if (!e) return fail("null handle");
   if (e->cfg.algo != LPC_ALGO_FISTA) return fail("lpc_fista_record: not a FISTA handle");
-  e->fista.rec_on = on > 0;
-  e->fista.tape_iters = -1;
-  if (on < 0) return 0;                                    // pause: the tape stays allocated, nothing is recorded
-  if (!e->fista.rec_on) { gd_tape_free(e); return 0; }
-  return e->fista.sched_n > 0 ? gd_tape_alloc(e) : 0;     // (no schedule yet: lpc_reset allocates)
+  return tape_record(e, e->fista_tape, on, gd_tape_alloc);
+}
+
+// the two refusals of a backward (`who`: fista / admm) whose tape does not hold the schedule's n iterations since the last
+// reset: nothing recorded at all, or (counted) not exactly n.  Two calls, because lpc_fista_backward has a refusal between
+static int tape_refusal(const Engine* e, const Tape& t, long n, const std::string& who, bool counted) {
+  if (!counted && (!t.rec_on || !t.buf || t.iters < 0))
+    return fail("lpc_" + who + "_backward: nothing recorded (lpc_" + who + "_record(h, 1), then lpc_reset and lpc_iterate)");
+  if (counted && !t.complete(n, e->iters_done))
+    return fail("lpc_" + who + "_backward: " + std::to_string(e->iters_done) + " iterations since the reset, the schedule has " +
+                std::to_string(n));
+  return 0;
 }
 
 static int fista_backward(lpc_handle e, const real* dev_grad_out, real* dev_grad_data, real* dev_grad_alpha,
@@ -226,12 +233,9 @@ static int fista_backward(lpc_handle e, const real* dev_grad_out, real* dev_grad
   if (!e || !dev_grad_out || !dev_grad_alpha || !dev_grad_coef) return fail("lpc_fista_backward: null argument");
   if (e->cfg.algo != LPC_ALGO_FISTA) return fail("lpc_fista_backward: not a FISTA handle");
   if (e->fista.sched_n <= 0) return fail("lpc_fista_backward: the handle has no schedule (lpc_set_fista_schedule)");
-  if (!e->fista.rec_on || !e->fista.tape || e->fista.tape_iters < 0)
-    return fail("lpc_fista_backward: nothing recorded (lpc_fista_record(h, 1), then lpc_reset and lpc_iterate)");
+  LPC_OK(tape_refusal(e, e->fista_tape, e->fista.sched_n, "fista", false));
   if (e->gd.split_pending) return fail("lpc_fista_backward: a split iteration is in flight (lpc_iterate_end missing)");
-  if (e->iters_done != e->fista.sched_n || e->fista.tape_iters != e->fista.sched_n || e->fista.tape_n != e->fista.sched_n)
-    return fail("lpc_fista_backward: " + std::to_string(e->iters_done) + " iterations since the reset, the schedule has " +
-                std::to_string(e->fista.sched_n));
+  LPC_OK(tape_refusal(e, e->fista_tape, e->fista.sched_n, "fista", true));
   if ((e->g.Hp | e->g.Wp) & 1)
     return fail("lpc_fista_backward: padded frame " + std::to_string(e->g.Hp) + " x " + std::to_string(e->g.Wp) +
                 " has an odd length: convolve and deconvolve are not each other's adjoints there (not implemented)");
@@ -255,11 +259,7 @@ int lpc_fista_backward_psf(lpc_handle e, const real* dev_grad_out, real* dev_gra
 int lpc_admm_record(lpc_handle e, int on) {
   if (!e) return fail("null handle");
   if (e->cfg.algo != LPC_ALGO_ADMM) return fail("lpc_admm_record: not an ADMM handle");
-  e->atape.rec_on = on > 0;
-  e->atape.tape_iters = -1;
-  if (on < 0) return 0;                                    // pause: the tape stays allocated, nothing is recorded
-  if (!e->atape.rec_on) { admm_tape_free(e); return 0; }
-  return e->admm.sched[0].empty() ? 0 : admm_tape_alloc(e);     // (no schedule yet: lpc_reset allocates)
+  return tape_record(e, e->admm_tape, on, admm_tape_alloc);
 }
 
 static int admm_backward_checked(lpc_handle e, const real* dev_grad_out, real* dev_grad_data, real* dev_grad_mu1,
@@ -277,11 +277,8 @@ static int admm_backward_checked(lpc_handle e, const real* dev_grad_out, real* d
   if (e->admm.custom_gram || e->admm.pnp_mode)
     return fail("lpc_admm_backward: a caller's psi and plug-and-play iterations are not differentiated");
   if (e->has_init) return fail("lpc_admm_backward: an initial estimate is set (its gradient is not implemented)");
-  if (!e->atape.rec_on || !e->atape.tape || e->atape.tape_iters < 0)
-    return fail("lpc_admm_backward: nothing recorded (lpc_admm_record(h, 1), then lpc_reset and lpc_iterate)");
-  if (e->iters_done != n || e->atape.tape_iters != n || e->atape.tape_n != n)
-    return fail("lpc_admm_backward: " + std::to_string(e->iters_done) + " iterations since the reset, the schedule has " +
-                std::to_string(n));
+  LPC_OK(tape_refusal(e, e->admm_tape, n, "admm", false));
+  LPC_OK(tape_refusal(e, e->admm_tape, n, "admm", true));
   if (dev_grad_data && !e->data_set) return fail("lpc_admm_backward: no data set");
   if (dev_grad_psf && e->cfg.norm != LPC_NORM_BACKWARD)
     return fail("lpc_admm_backward_psf: the gradient with respect to the PSF is implemented for norm \"backward\" only");

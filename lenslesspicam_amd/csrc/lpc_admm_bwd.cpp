@@ -3,63 +3,41 @@
 // lpc_admm_bwd_kernels.h; the spectral step of the sweep is the forward's own (lpc_admm.cpp: admm_spectral_plain).
 #include "lpc_engine.h"
 #include "lpc_admm_bwd_kernels.h"
-#include "lpc_gd_bwd_kernels.h"      // k_gd_bwd_gdata: planar data gradient -> the measurement's layout
 
 static constexpr int kBwdTH = 8, kBwdQW = 32;      // k_admm_bwd_step: tiles of 8 rows x 128 columns on 256 lanes
 static inline long bwd_tiles_x(const PlaneGeom& g) { return (g.Wp + 4 * kBwdQW - 1) / (4 * kBwdQW); }
 static inline long bwd_tiles(const PlaneGeom& g) { return bwd_tiles_x(g) * ((g.Hp + kBwdTH - 1) / kBwdTH); }
 
-void admm_tape_free(Engine* e) {
-  AdmmTape& t = e->atape;
-  dev_free(e, t.psf_ws);         // the PSF gradient's workspace goes with the tape
-  t.psf_ws = nullptr;
-  if (!t.tape) return;
-  dev_free(e, t.tape);
-  dev_free(e, t.part);
-  t.tape = nullptr; t.part = nullptr; t.tape_n = 0; t.tape_iters = -1;
-}
-
+// ---- the tape (struct Tape, lpc_engine.h): 6 n + 11 padded state arrays ----
 int admm_tape_alloc(Engine* e) {
-  AdmmTape& t = e->atape;
-  const int n = (int)e->admm.sched[0].size();
-  if (t.tape && t.tape_n == n) return 0;
-  admm_tape_free(e);
-  const size_t rp = (size_t)e->g.rplane * e->P;
-  LPC_OK(dev_alloc(e, &t.tape, (size_t)(6 * n + 11) * rp));
-  if (dev_alloc(e, &t.part, (size_t)n * e->P * bwd_tiles(e->g) * 4)) {      // all or nothing
-    admm_tape_free(e);
-    return 1;
-  }
-  t.tape_n = n;
-  return 0;
+  const size_t n = e->admm.sched[0].size();
+  if (!n) return 0;
+  return tape_alloc(e, e->admm_tape, (int)n, 6 * n + 11, (size_t)e->g.rplane * e->P, n * e->P * bwd_tiles(e->g) * 4);
 }
-
-// slots of the tape, in padded state arrays (AdmmTape)
-static inline real* tape_slot(Engine* e, long k) { return e->atape.tape + (size_t)k * e->g.rplane * e->P; }
-static inline real* tape_v(Engine* e, int i) { return tape_slot(e, i); }
-static inline real* tape_hv(Engine* e, int i) { return tape_slot(e, e->atape.tape_n + 1 + i); }
+static inline real* tape_v(Engine* e, int i) { return e->admm_tape.at(i); }
+static inline real* tape_hv(Engine* e, int i) { return e->admm_tape.at(e->admm_tape.n + 1 + i); }
 static inline real* tape_dual(Engine* e, int which, int i) {      // which: 0 xi, 1 eta0, 2 eta1, 3 rho
-  return tape_slot(e, 2 * (e->atape.tape_n + 1) + (long)which * e->atape.tape_n + i);
+  return e->admm_tape.at(2 * (e->admm_tape.n + 1) + (long)which * e->admm_tape.n + i);
 }
-static inline real* tape_work(Engine* e, int k) { return tape_slot(e, 6 * e->atape.tape_n + 2 + k); }
+static inline real* tape_work(Engine* e, int k) { return e->admm_tape.at(6 * e->admm_tape.n + 2 + k); }
 
 int admm_tape_reset(Engine* e) {
-  AdmmTape& t = e->atape;
-  t.tape_iters = -1;
+  Tape& t = e->admm_tape;
+  t.invalidate();
   // (an initial estimate, a caller's psi and plug-and-play iterations are not differentiated: nothing is recorded, and
   // lpc_admm_backward says why)
   if (!t.rec_on || e->admm.sched[0].empty() || e->has_init) return 0;
   LPC_OK(admm_tape_alloc(e));
-  LPC_RT(rt::memset_async(tape_v(e, 0), 0, (size_t)e->g.rplane * e->P * sizeof(real), e->stream));     // V_0
-  t.tape_iters = 0;
+  LPC_RT(rt::memset_async(tape_v(e, 0), 0, t.slot * sizeof(real), e->stream));     // V_0
+  t.begin();
   return 0;
 }
 
 int admm_tape_push(Engine* e, const real* Vnew) {
-  AdmmTape& t = e->atape;
-  if (t.tape_iters < 0 || t.tape_iters != e->iters_done || e->iters_done >= t.tape_n) return 0;
-  LPC_RT(rt::copy_d2d_async(tape_v(e, (int)e->iters_done + 1), Vnew, (size_t)e->g.rplane * e->P * sizeof(real), e->stream));
-  ++t.tape_iters;
+  Tape& t = e->admm_tape;
+  if (!t.wants(e->iters_done)) return 0;
+  LPC_RT(rt::copy_d2d_async(tape_v(e, (int)e->iters_done + 1), Vnew, t.slot * sizeof(real), e->stream));
+  t.advance();
   return 0;
 }
 
@@ -92,14 +70,15 @@ static int psf_spectrum(Engine* e, const real* x, real2* S) {
 int admm_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_mu1, real* grad_mu2, real* grad_mu3,
                   real* grad_tau, real* grad_psf) {
   const PlaneGeom& g = e->g;
-  const int n = e->atape.tape_n;
+  Tape& t = e->admm_tape;
+  const int n = t.n;
   const size_t rb_bytes = (size_t)g.rplane * e->P * sizeof(real);
   const dim3 pw = grid1d((long)g.Hp * g.Wp, 256, e->P);
   const size_t sp = (size_t)g.cplane * e->P;
   real2 *FV = nullptr, *FR = nullptr, *FA = nullptr, *FB = nullptr, *acc = nullptr;
   if (grad_psf) {
-    if (!e->atape.psf_ws) LPC_OK(dev_alloc(e, &e->atape.psf_ws, 4 * sp + (size_t)g.cplane * g.C));
-    FV = e->atape.psf_ws; FR = FV + sp; FA = FR + sp; FB = FA + sp; acc = FB + sp;
+    if (!t.psf_ws) LPC_OK(dev_alloc(e, &t.psf_ws, 2 * (4 * sp + (size_t)g.cplane * g.C)));      // (in reals: spectra)
+    FV = (real2*)t.psf_ws; FR = FV + sp; FA = FR + sp; FB = FA + sp; acc = FB + sp;
   }
 
   // ---- replay: H V_i and the duals every iteration started from ----
@@ -150,7 +129,7 @@ int admm_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_m
     a.eb0 = tape_work(e, 2 + 2 * cur); a.eb1 = tape_work(e, 3 + 2 * cur);
     a.eb0o = tape_work(e, 2 + 2 * (cur ^ 1)); a.eb1o = tape_work(e, 3 + 2 * (cur ^ 1));
     a.gb = gb; a.Rsp = e->admm.Rsp; a.Aarr = e->admm.Aarr;
-    a.part = e->atape.part + (size_t)i * e->P * tiles * 4;
+    a.part = t.part + (size_t)i * e->P * tiles * 4;
     LPC_OK(launch_k(e, -1, k_admm_bwd_step<kBwdTH, kBwdQW>, dim3((unsigned)tiles, e->P, 1), kBwdTH * kBwdQW,
                     admm_bwd_step_smem<kBwdTH, kBwdQW>(), g, bwd_scalars(e, i, n), a, (unsigned)bwd_tiles_x(g)));
     cur ^= 1;
@@ -158,9 +137,7 @@ int admm_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_m
                     (long)e->P * tiles, par[3] / (par[1] * par[1]), 1.0 / par[1], grad_mu1 + i, grad_mu2 + i, grad_mu3 + i,
                     grad_tau + i));
   }
-  if (grad_data)
-    LPC_OK(launch_k(e, -1, k_gd_bwd_gdata<256>, grid1d(g.uplane, 256, e->cfg.batch), 256, 0, (const real*)gb, grad_data,
-                    (long)g.uplane, e->cfg.channels, e->data_channels));
+  if (grad_data) LPC_OK(gd_bwd_gdata(e, gb, grad_data));
   if (grad_psf) {
     // rbar, hr are free again: one padded plane with a unit impulse at the origin, read as every channel's plane
     LPC_RT(rt::memset_async(rbar, 0, (size_t)g.rplane * sizeof(real), e->stream));

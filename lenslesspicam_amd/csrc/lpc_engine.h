@@ -10,15 +10,16 @@
 //   lpc_setup.cpp    twiddles and plans, geometry set-up, the common workspace, PSF spectrum, the bare operator, and the
 //                    host helpers every algorithm shares with their layout / fill / min-max kernels
 //   lpc_admm.cpp     ADMM: host sequences and every image-domain ADMM kernel
-//   lpc_gd_host.cpp  the gradient-descent family: host sequences, the tape and the reverse sweep
+//   lpc_gd_host.cpp  the gradient-descent family: host sequences of the forward iterations
 //   lpc_eval.cpp     evaluation reductions and the handle-free raw-frame / resize paths
 //   lpc_rows.cpp     every row-pass launch (real <-> half-spectrum transforms, incl. the fused ADMM rows)
 //   lpc_cols.cpp     every column-pass launch (pass A, the fused middles)
 //   lpc_gd.cpp, lpc_gd_update.cpp, lpc_gd_update_p0.cpp, lpc_gd_update_p1.cpp   the gradient-descent family's fused row
 //                    kernels (the update rows in three units: half-length rows, paired rows without / with the folded
 //                    radix-2 stage)
-//   lpc_gd_bwd.cpp   reverse mode of unrolled FISTA: the fused row kernels of lpc_fista_backward
-//   lpc_admm_bwd.cpp reverse mode of unrolled ADMM: the tape of iterates, the replay and the sweep of lpc_admm_backward
+//   lpc_gd_bwd.cpp   reverse mode of unrolled FISTA: its tape's layout, the sweep of lpc_fista_backward and its fused row
+//                    kernels
+//   lpc_admm_bwd.cpp reverse mode of unrolled ADMM: its tape's layout, the replay and the sweep of lpc_admm_backward
 //   lpc_jit.cpp      plan modules: find / compile / load (lpc_plan.h)
 //   lpc_module.cpp   NOT part of the library: the source of a plan module (compile-time-plan kernels of one frame shape)
 #pragma once
@@ -166,23 +167,6 @@ struct AdmmState {
   bool custom_gram = false;    // lpc_set_psi_gram replaced the finite-difference gram (until the next lpc_set_psf)
 };
 
-// reverse mode of unrolled ADMM (lpc_admm_record / lpc_admm_backward; lpc_admm_bwd.cpp).  ONE allocation of 6 n + 11 padded
-// state arrays for a schedule of n iterations:
-//   V_0 .. V_n | H V_0 .. H V_n | xi_0 .. xi_{n-1} | eta0_i | eta1_i | rho_i | work: xib, rhob, etab0[0], etab1[0],
-//   etab0[1], etab1[1], rb, hr | g_b (un-padded planes inside a padded array's room)
-// The recorded forward writes V_i only; the backward's replay fills in the rest.  `part`: the partial sums of the four
-// reductions, 4 doubles per workgroup of k_admm_bwd_step and iteration.
-struct AdmmTape {
-  bool rec_on = false;
-  real* tape = nullptr;
-  double* part = nullptr;
-  int tape_n = 0;              // iterations the tape was allocated for
-  long tape_iters = -1;        // iterations recorded since the last reset (-1: nothing recorded)
-  // PSF gradient (lpc_admm_backward_psf), allocated at its first call and freed with the tape: four work spectra of P
-  // planes (F V_{i+1}, F rb, F a_i, F ab) and the accumulator, C planes
-  real2* psf_ws = nullptr;
-};
-
 // gradient-descent family: state (un-padded planes)
 struct GdState {
   real *gx = nullptr, *gaux = nullptr;  // x and (p | xk_prev)
@@ -195,27 +179,41 @@ struct GdState {
   bool split_pending = false;  // lpc_iterate_begin ran, lpc_iterate_end has not yet
 };
 
-// unrolled FISTA (unrolled_fista.py:91-106): per-iteration step alpha[i][c] and momentum factor coef[i], and the tape of
-// the reverse mode
+// unrolled FISTA (unrolled_fista.py:91-106): per-iteration step alpha[i][c] and momentum factor coef[i]
 struct FistaSchedule {
   std::vector<real> coef;
   real* galpha_sched = nullptr;  // device [n][C]
   size_t sched_cap = 0;          // elements allocated for it (re-used by later schedules that fit)
   int sched_n = 0;
   std::vector<real> alpha;       // host copy of the schedule's alpha (lpc_fista_backward refuses a zero step)
-  // reverse mode (lpc_fista_record / lpc_fista_backward): the tape is ONE allocation of (2 n + 4) un-padded state arrays
-  //   y_0 .. y_n | xk_0 .. xk_{n-1} | work: gy / gz, carry, g_b      (y_i = gx before iteration i, xk_i = gaux after it)
-  // and the per-row partial sums of g_coef / g_alpha: n * P * H * 2 doubles
+};
+
+// The tape of a reverse mode (lpc_fista_record / lpc_admm_record; tape_alloc .. tape_record below).  ONE allocation of state
+// arrays (`slot` elements each) for a schedule of n iterations, plus the per-workgroup partial sums of the sweep's reductions:
+//   FISTA (lpc_gd_bwd.cpp), 2 n + 4 un-padded arrays:  y_0 .. y_n | xk_0 .. xk_{n-1} | work: gy / gz, carry, g_b
+//       (y_i = gx before iteration i, xk_i = gaux after it); part: n * P * H * 2 doubles (g_coef / g_alpha per row)
+//   ADMM (lpc_admm_bwd.cpp), 6 n + 11 padded arrays:  V_0 .. V_n | H V_0 .. H V_n | xi_0 .. xi_{n-1} | eta0_i | eta1_i |
+//       rho_i | work: xib, rhob, etab0[0], etab1[0], etab0[1], etab1[1], rb, hr | g_b (un-padded planes inside a padded
+//       array's room).  The recorded forward writes V_i only; the backward's replay fills in the rest.  part: 4 doubles per
+//       workgroup of k_admm_bwd_step and iteration
+// psf_ws, the PSF gradient's workspace, is ONE allocation too, made at its first call and freed with the tape:
+//   FISTA: three spectrum buffers of P planes (residual rows / cross term; full spectrum of P gz_i / rows of P Hg_i; full
+//       spectrum of P y_i) | the accumulator, P un-padded planes
+//   ADMM: four work spectra of P planes (F V_{i+1}, F rb, F a_i, F ab) | the accumulator, C spectrum planes
+struct Tape {
   bool rec_on = false;
-  real* tape = nullptr;
-  double* tape_part = nullptr;
-  int tape_n = 0;              // iterations the tape was allocated for
-  // PSF gradient (lpc_fista_backward_psf), allocated at its first call and freed with the tape: three spectrum buffers of P
-  // planes (residual rows / cross term; full spectrum of P gz_i / rows of P Hg_i; full spectrum of P y_i) and the
-  // accumulator, P un-padded planes
-  real2* psf_spec = nullptr;
-  real* psf_acc = nullptr;
-  long tape_iters = -1;        // iterations recorded since the last reset (-1: nothing recorded)
+  real* buf = nullptr;
+  size_t slot = 0;             // elements of one state array
+  double* part = nullptr;
+  int n = 0;                   // iterations the tape was allocated for
+  long iters = -1;             // iterations recorded since the last reset (-1: nothing recorded)
+  real* psf_ws = nullptr;
+  real* at(long k) const { return buf + (size_t)k * slot; }
+  void begin() { iters = 0; }
+  void invalidate() { iters = -1; }      // what was recorded no longer matches the schedule / data / state: backward refuses
+  bool wants(long iters_done) const { return iters >= 0 && iters == iters_done && iters_done < n; }   // push this iteration?
+  void advance() { ++iters; }
+  bool complete(long sched_n, long iters_done) const { return iters_done == sched_n && iters == sched_n && n == sched_n; }
 };
 
 struct lpc_engine : LaunchCtx {
@@ -251,7 +249,7 @@ struct lpc_engine : LaunchCtx {
   AdmmState admm;
   GdState gd;
   FistaSchedule fista;
-  AdmmTape atape;
+  Tape fista_tape, admm_tape;
 };
 typedef lpc_engine Engine;
 
@@ -276,6 +274,36 @@ static inline void dev_free(Engine* e, void* p) {
       break;
     }
   (void)rt::dev_free(p);
+}
+
+// ---- the tape of a reverse mode (struct Tape): what unrolled FISTA and unrolled ADMM do alike ----
+static inline void tape_free(Engine* e, Tape& t) {
+  dev_free(e, t.psf_ws);         // the PSF gradient's workspace goes with the tape
+  dev_free(e, t.buf);
+  dev_free(e, t.part);
+  t.psf_ws = nullptr; t.buf = nullptr; t.part = nullptr; t.n = 0;
+  t.invalidate();
+}
+// for n iterations: nslots state arrays of `slot` elements and nparts partial sums, all or nothing (allocated for n: no-op)
+static inline int tape_alloc(Engine* e, Tape& t, int n, size_t nslots, size_t slot, size_t nparts) {
+  if (t.buf && t.n == n) return 0;
+  tape_free(e, t);
+  LPC_OK(dev_alloc(e, &t.buf, nslots * slot));
+  if (dev_alloc(e, &t.part, nparts)) {
+    tape_free(e, t);
+    return 1;
+  }
+  t.n = n; t.slot = slot;
+  return 0;
+}
+// lpc_fista_record / lpc_admm_record: on > 0 records, on < 0 pauses (the tape stays allocated, nothing is recorded), 0 frees.
+// alloc: the solver's gd_tape_alloc / admm_tape_alloc, which does nothing without a schedule (lpc_reset allocates then)
+static inline int tape_record(Engine* e, Tape& t, int on, int (*alloc)(Engine*)) {
+  t.rec_on = on > 0;
+  t.invalidate();
+  if (on < 0) return 0;
+  if (!t.rec_on) { tape_free(e, t); return 0; }
+  return alloc(e);
 }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: the (device, function) pairs that have
@@ -422,8 +450,7 @@ int admm_kernel_bytes(Engine* e, int kid, double* bytes);
 double admm_model_bytes(const Engine* e);
 int admm_spectral_plain(Engine* e, const double par[4], real* Vout, real* HVout);   // (Rsp, Aarr) -> S(Rsp + HT Aarr), H of it, with par's R_divmat
 // lpc_admm_bwd.cpp
-void admm_tape_free(Engine* e);
-int admm_tape_alloc(Engine* e);
+int admm_tape_alloc(Engine* e);                    // for the handle's schedule (none yet: nothing, lpc_reset allocates)
 int admm_tape_reset(Engine* e);                    // admm_reset: V_0, or nothing when the handle does not record
 int admm_tape_push(Engine* e, const real* Vnew);   // admm_iterate: the iterate an iteration just wrote
 int admm_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_mu1, real* grad_mu2, real* grad_mu3,
@@ -432,14 +459,10 @@ int admm_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_m
 int gd_alloc(Engine* e);
 int gd_setup_constants(Engine* e);
 int gd_apply_momentum_reset(Engine* e);
-void gd_tape_free(Engine* e);
-int gd_tape_alloc(Engine* e);
 int gd_set_schedule(Engine* e, int n, const real* alpha, const real* coef);
 int gd_reset(Engine* e);
 int gd_iterate(Engine* e, int n_iter, int split = 0);
 int gd_finish_split(Engine* e, const real* dev_projected);
-int gd_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_alpha, real* grad_coef, real* grad_init,
-                real* grad_psf = nullptr);
 int gd_form_image(Engine* e, real* dev_out);
 int gd_get_state(Engine* e, const std::string& nm, real* dev_out);
 int gd_kernel_bytes(Engine* e, int kid, double* bytes);
@@ -461,7 +484,13 @@ int admm_cols(Engine* e, const AdmmScalars& sc);   // sc.skipa: forward pass A r
 int gd_rows_mid(Engine* e, const real2* Sin, real2* Sout);      // irfft rows -> residual -> rfft rows (the iteration: S -> S2)
 int gd_rows_update(Engine* e, const GdScalars& sc, const real* alpha);   // irfft rows -> fused projected update
 // lpc_gd_bwd.cpp
+int gd_tape_alloc(Engine* e);                      // for the handle's schedule (none yet: nothing, lpc_reset allocates)
+int gd_tape_reset(Engine* e);                      // gd_reset: y_0, or nothing when the handle does not record
+int gd_tape_push(Engine* e);                       // gd_iterate: what the update of an iteration just wrote
+int gd_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_alpha, real* grad_coef, real* grad_init,
+                real* grad_psf = nullptr);
 int gd_bwd_rows(Engine* e, int mode, const GdBwd& a, const real2* Sin = nullptr);   // reverse-mode rows: 0 head, 1 middle, 2 update + next head, 3 PSF-gradient accumulate (rows of Sin)
 int gd_bwd_psf_sum(Engine* e, const real* acc, real* grad_psf); // ... and its sum over the batch -> (1, H, W, C)
+int gd_bwd_gdata(Engine* e, const real* gb, real* grad_data);   // planar data gradient -> the measurement's layout (both sweeps)
 
 #include "lpc_launch.h"

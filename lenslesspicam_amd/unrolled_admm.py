@@ -47,31 +47,18 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
+from ._unrolled import _Estimate, _Taped, _grad_like, _meta      # noqa: F401 (_Estimate: imported from here too)
 from .admm import ADMM
 
 _NAMES = ("_mu1_p", "_mu2_p", "_mu3_p", "_tau_p")
-
-
-class _Estimate(torch.Tensor):
-    """What ``forward()`` returns under autograd.  The parameters require a gradient by default, so code that only wants
-    the image -- ``out.cpu().numpy()``, ``np.asarray(out)`` -- gets a tensor with a graph behind it where it used to get
-    a plain one; this one still converts to NumPy (of its detached values), and is an ordinary tensor otherwise."""
-
-    def numpy(self, *args, **kwargs):
-        return self.detach().as_subclass(torch.Tensor).numpy(*args, **kwargs)
-
-    def __array__(self, dtype=None, copy=None):
-        a = self.numpy()
-        return a if dtype is None else a.astype(dtype, copy=False)
 
 
 class _UnrolledADMMFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rec, batch, mu1_p, mu2_p, mu3_p, tau_p, psf=None):
         out = rec._run(batch, record=rec._backward_refusal() is None)
-        ctx.psf_meta = None if psf is None else (tuple(psf.shape), psf.dtype, psf.device)
         ctx.rec, ctx.gen = rec, rec._tape_gen
-        ctx.batch_meta = (tuple(batch.shape), batch.dtype, batch.device)
+        ctx.batch_meta, ctx.psf_meta = _meta(batch), _meta(psf)
         ctx.save_for_backward(mu1_p, mu2_p, mu3_p, tau_p)
         return out
 
@@ -84,8 +71,7 @@ class _UnrolledADMMFunction(torch.autograd.Function):
         why = rec._backward_refusal()
         if why is not None:
             raise NotImplementedError("UnrolledADMM.backward: " + why)
-        if ctx.gen != rec._tape_gen:
-            raise RuntimeError("UnrolledADMM.backward: tape overwritten by a later forward() of the same solver")
+        rec._check_tape(ctx.gen)
         n = rec._n_iter
         need_b = ctx.needs_input_grad[1]
         need_p = ctx.psf_meta is not None and ctx.needs_input_grad[6]
@@ -109,15 +95,14 @@ class _UnrolledADMMFunction(torch.autograd.Function):
                 q = p.detach().requires_grad_()
                 v = rec._schedule_of(q)
                 grads.append(torch.autograd.grad(v, q, g_par[k].to(device=v.device, dtype=v.dtype))[0])
-        gb = g_data[:, None].to(device=ctx.batch_meta[2], dtype=ctx.batch_meta[1]) if need_b else None
-        gp = None
-        if need_p:
-            shape, dtype, device = ctx.psf_meta
-            gp = g_psf.reshape(shape).to(device=device, dtype=dtype)
+        gb = _grad_like(g_data[:, None], ctx.batch_meta) if need_b else None
+        gp = _grad_like(g_psf, ctx.psf_meta) if need_p else None
         return (None, gb) + tuple(grads) + (gp,)
 
 
-class UnrolledADMM(ADMM, torch.nn.Module):
+class UnrolledADMM(_Taped, ADMM, torch.nn.Module):
+    _record_method, _solver = "admm_record", "UnrolledADMM"
+
     def __init__(self, psf, dtype=None, n_iter=5, mu1=1e-6, mu2=1e-5, mu3=4e-5, tau=0.0001, psi=None,
                  psi_adj=None, psi_gram=None, pad=False, norm="backward", skip_unrolled=False, psf_grad=False, **kwargs):
         for key in ("pre_process", "post_process", "background_network", "psf_network", "compensation"):
@@ -135,8 +120,7 @@ class UnrolledADMM(ADMM, torch.nn.Module):
         for name, val in zip(_NAMES, (mu1, mu2, mu3, tau)):
             v = torch.ones(n_iter, dtype=torch.float32, device=psf.device) * val
             setattr(self, name, v if skip_unrolled else torch.nn.Parameter(v))
-        self._tape_gen = 0
-        self._rec_state = (None, False)
+        self._tape_init()
         self._push_schedule()
 
     def set_parameters(self, mu1=None, mu2=None, mu3=None, tau=None):
@@ -170,27 +154,10 @@ class UnrolledADMM(ADMM, torch.nn.Module):
             self._push_schedule()
         super().reset()
 
-    def _record(self, on):
-        """the handle keeps its iterates from the next reset on, or stops: a forward without gradients between two
-        training steps pauses the recording and keeps the tape's memory (no wait for the stream, no allocation)"""
-        state = (self._handle, bool(on))
-        if on or self._rec_state[0] is self._handle:      # (a handle that never recorded has nothing to pause)
-            if state != self._rec_state:
-                self._handle.admm_record(1 if on else -1)
-                self._rec_state = state
-
-    def release_tape(self):
-        """gives the tape's device memory back (it returns with the next forward that needs gradients)"""
-        if self._rec_state[0] is self._handle:
-            self._handle.admm_record(0)
-        self._rec_state = (None, False)
-        self._tape_gen += 1
-
     def _run(self, batch, record=False):
         self._data = batch
         self._upload_data()
-        self._tape_gen += 1            # reset() starts the tape over: gradients of earlier forwards are gone
-        self._record(record)
+        self._new_tape(record)
         self.reset()
         self._iterate(self._n_iter)
         return self._form_image()
@@ -222,17 +189,12 @@ class UnrolledADMM(ADMM, torch.nn.Module):
     def forward(self, batch, psfs=None, background=None):
         """``batch``: (B, D=1, H, W, C) measurements -> (B, D, H, W, C) estimates after exactly
         ``n_iter`` unrolled iterations (trainable_recon.py:297-405 without the learned stages)."""
-        assert isinstance(batch, torch.Tensor) and len(batch.shape) == 5, "batch must be of shape (N, D, H, W, C)"
-        if background is not None:
-            raise NotImplementedError("background subtraction networks are outside the hot path")
+        self._check_forward_args(batch, psfs, background)
         params = [getattr(self, n) for n in _NAMES]
         psf_grad = (isinstance(psfs, torch.Tensor) and psfs.requires_grad) or \
             (isinstance(self._psf, torch.Tensor) and self._psf.requires_grad)
         init_grad = isinstance(self._initial_est, torch.Tensor) and self._initial_est.requires_grad
         train = torch.is_grad_enabled() and (psf_grad or init_grad or any(t.requires_grad for t in [batch] + params))
-        if isinstance(psfs, torch.Tensor) and psfs.dim() == 5:
-            raise NotImplementedError("UnrolledADMM: per-frame PSFs (a 5-D psfs) are not implemented: one PSF for the "
-                                      "batch")
         if train:
             self._refuse_gradients(batch, psfs if psf_grad else None)
         if psfs is not None:

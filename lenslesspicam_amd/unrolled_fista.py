@@ -31,6 +31,7 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
+from ._unrolled import _Taped, _grad_like, _meta
 from .gd import FISTA, non_neg
 
 
@@ -38,10 +39,8 @@ class _UnrolledFISTAFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rec, batch, alpha_p, tk_p, init, psf):
         out = rec._run(batch, record=True, push_init=init is not None)
-        ctx.psf_meta = None if psf is None else (tuple(psf.shape), psf.dtype, psf.device)
         ctx.rec, ctx.gen = rec, rec._tape_gen
-        ctx.batch_meta = (tuple(batch.shape), batch.dtype, batch.device)
-        ctx.init_meta = None if init is None else (tuple(init.shape), init.dtype, init.device)
+        ctx.batch_meta, ctx.init_meta, ctx.psf_meta = _meta(batch), _meta(init), _meta(psf)
         ctx.save_for_backward(alpha_p, tk_p)
         return out
 
@@ -56,8 +55,7 @@ class _UnrolledFISTAFunction(torch.autograd.Function):
             raise NotImplementedError(
                 f"UnrolledFISTA.backward: padded frame {rec._padded_shape[1]} x {rec._padded_shape[2]} has an odd "
                 "length (convolve and deconvolve are not each other's adjoints there)")
-        if ctx.gen != rec._tape_gen:
-            raise RuntimeError("UnrolledFISTA.backward: tape overwritten by a later forward() of the same solver")
+        rec._check_tape(ctx.gen)
         h, n, C = rec._handle, rec._n_iter, int(rec._psf_shape[3])
         need_b, need_a, need_t, need_i, need_p = ctx.needs_input_grad[1:6]
         g = rec._to_dev(grad_out)
@@ -79,20 +77,18 @@ class _UnrolledFISTAFunction(torch.autograd.Function):
             alpha, coef = rec._schedule_of(ap, tp)
             ga = torch.autograd.grad(alpha, ap, g_a.to(device=alpha.device, dtype=alpha.dtype))[0] if need_a else None
             gt = torch.autograd.grad(coef, tp, g_c.to(device=coef.device, dtype=coef.dtype))[0] if need_t else None
-        gb = gi = gp = None
-        if need_b:
-            gb = g_data[:, None].to(device=ctx.batch_meta[2], dtype=ctx.batch_meta[1])
+        gb = _grad_like(g_data[:, None], ctx.batch_meta) if need_b else None
+        gi = None
         if need_i:
-            shape, dtype, device = ctx.init_meta
-            gi = g_init if shape[0] == g_init.shape[0] else g_init.sum(0, keepdim=True)     # one estimate for the batch
-            gi = gi.reshape(shape).to(device=device, dtype=dtype)
-        if need_p:
-            shape, dtype, device = ctx.psf_meta
-            gp = g_psf.reshape(shape).to(device=device, dtype=dtype)
+            one = ctx.init_meta[0][0] != g_init.shape[0]      # one estimate for the batch
+            gi = _grad_like(g_init.sum(0, keepdim=True) if one else g_init, ctx.init_meta)
+        gp = _grad_like(g_psf, ctx.psf_meta) if need_p else None
         return None, gb, ga, gt, gi, gp
 
 
-class UnrolledFISTA(FISTA, torch.nn.Module):
+class UnrolledFISTA(_Taped, FISTA, torch.nn.Module):
+    _record_method, _solver = "fista_record", "UnrolledFISTA"
+
     def __init__(self, psf, n_iter=5, dtype=None, proj=non_neg, learn_tk=True, tk=1, skip_unrolled=False, **kwargs):
         assert isinstance(psf, torch.Tensor), "UnrolledFISTA takes torch tensors, like the reference"
         torch.nn.Module.__init__(self)
@@ -111,8 +107,7 @@ class UnrolledFISTA(FISTA, torch.nn.Module):
         self._alpha_p = alpha if skip_unrolled else torch.nn.Parameter(alpha)
         self._tk_p = torch.nn.Parameter(tk_p) if learn_tk and not skip_unrolled else tk_p
         self._sched_key = None
-        self._tape_gen = 0
-        self._rec_state = (None, False)
+        self._tape_init()
         # unrolled_fista.py:55-59: `_image_init` is computed here, from this PSF, and reset() (:91-96) reuses it whatever PSF
         # forward(batch, psfs=...) or _set_psf() made current since -- unlike gd.py:94-112, which follows the PSF.  The
         # handle computed it in lpc_set_psf; every handle of this solver is pinned to these values.
@@ -164,43 +159,21 @@ class UnrolledFISTA(FISTA, torch.nn.Module):
             self._push_schedule()
         super().reset()
 
-    def _record(self, on):
-        """the handle records its tape from the next reset on, or stops: a forward without gradients between two
-        training steps pauses the recording and keeps the tape's memory (no wait for the stream, no allocation)"""
-        state = (self._handle, bool(on))
-        if on or self._rec_state[0] is self._handle:      # (a handle that never recorded has nothing to pause)
-            if state != self._rec_state:
-                self._handle.fista_record(1 if on else -1)
-                self._rec_state = state
-
-    def release_tape(self):
-        """gives the tape's device memory back (it returns with the next forward that needs gradients)"""
-        if self._rec_state[0] is self._handle:
-            self._handle.fista_record(0)
-        self._rec_state = (None, False)
-        self._tape_gen += 1
-
     def _run(self, batch, record=False, push_init=False):
         self._data = batch
         self._upload_data()
         if push_init:
             self._push_initial_estimate()      # the current values of an estimate that is being learnt
-        self._tape_gen += 1            # reset() starts the tape over: gradients of earlier forwards are gone
         self._push_schedule()
-        self._record(record)
+        self._new_tape(record)
         self.reset()
         self._iterate(self._n_iter)
         return self._form_image()
 
     def forward(self, batch, psfs=None, background=None):
         """``batch``: (B, D, H, W, C) -> (B, D, H, W, C) after exactly ``n_iter`` unrolled iterations."""
-        assert isinstance(batch, torch.Tensor) and len(batch.shape) == 5, "batch must be of shape (N, D, H, W, C)"
-        if background is not None:
-            raise NotImplementedError("background subtraction networks are outside the hot path")
+        self._check_forward_args(batch, psfs, background)
         if psfs is not None:
-            if isinstance(psfs, torch.Tensor) and psfs.dim() == 5:
-                raise NotImplementedError("UnrolledFISTA: per-frame PSFs (a 5-D psfs) are not implemented: one PSF "
-                                          "for the batch")
             self._set_psf(psfs)
         init = self._initial_est if isinstance(self._initial_est, torch.Tensor) else None
         psf = self._psf if isinstance(self._psf, torch.Tensor) and self._psf.requires_grad else None
