@@ -292,7 +292,11 @@ int lpc_iterate(lpc_handle h, int n_iter, void* stream);
  * 235-241; `proj=` argument gd.py:67, external denoiser gd.py:89-92).  lpc_iterate_begin runs the fused gradient /
  * momentum half and leaves the UNPROJECTED estimate readable as lpc_get_state("image_est"); the caller applies its
  * projection or denoiser to that (B,D,H,W,C) array and passes the result to lpc_iterate_end, which completes the
- * iteration (FISTA: the extrapolation and the t_k recursion).  Mixing with lpc_iterate between the two is an error. */
+ * iteration (FISTA: the extrapolation and the t_k recursion).  Mixing with lpc_iterate between the two is an error;
+ * whole iterations of either kind may follow one another.  On a handle with an unrolled schedule
+ * (lpc_set_fista_schedule) a split iteration takes its step and its momentum factor from the schedule's entry of that
+ * iteration, like a fused one; a handle that records a tape (lpc_fista_record) refuses lpc_iterate_begin: only the fused
+ * projection is differentiated. */
 int lpc_iterate_begin(lpc_handle h, void* stream);
 int lpc_iterate_end(lpc_handle h, const lpc_real* dev_projected, void* stream);
 

@@ -317,7 +317,8 @@ int lpc_iterate_begin(lpc_handle e, void* stream) {
   if (!e->psf_set) return fail("lpc_iterate_begin: PSF not set");
   if (!e->data_set) return fail("Must set data with `set_data()`");
   if (e->gd.split_pending) return fail("lpc_iterate_begin: the previous split iteration was not finished");
-  if (e->fista.sched_n > 0) return fail("lpc_iterate_begin: not available with an unrolled schedule");
+  if (e->fista_tape.rec_on)   // (the reverse sweep differentiates the fused projection only)
+    return fail("lpc_iterate_begin: not available while the handle records a tape (lpc_fista_record)");
   e->stream = (lpcStream_t)stream;
   return gd_iterate(e, 1, 1);
 }

@@ -132,8 +132,11 @@ int gd_iterate(Engine* e, int n_iter, int split) {
 int gd_finish_split(Engine* e, const real* dev_projected) {
   const PlaneGeom& g = e->g;
   const double tk_new = (1.0 + std::sqrt(1.0 + 4.0 * e->gd.tk * e->gd.tk)) / 2.0;  // gd.py:238
+  real coef = (real)((e->gd.tk - 1.0) / tk_new);
+  if (e->fista.sched_n > 0)    // unrolled FISTA: this iteration's factor, as gd_iterate takes it (x_k started as the initial image)
+    coef = e->fista.coef[(size_t)std::min<long>(e->iters_done, e->fista.sched_n - 1)];
   LPC_OK(launch_k(e, -1, k_gd_post<256>, grid1d(g.uplane, 256, e->P), 256, 0, g, dev_projected, e->gd.gx, e->gd.gaux,
-                  e->cfg.algo - LPC_ALGO_GD, (real)((e->gd.tk - 1.0) / tk_new)));
+                  e->cfg.algo - LPC_ALGO_GD, coef));
   if (e->cfg.algo == LPC_ALGO_FISTA) e->gd.tk = tk_new;
   e->first = false;
   e->gd.split_pending = false;

@@ -12,7 +12,9 @@ fused HIP kernels (``lpc_fista_backward`` / ``lpc_fista_backward_psf``, csrc/lpc
 ``(t_i - 1) / t_{i+1}`` on ``n_iter``-sized tensors.  There is one tape per solver: ``backward()`` after a later
 ``forward()`` of the same object raises; a forward without gradients in between keeps the tape's memory
 (``release_tape()`` gives it back).  Not differentiated (``NotImplementedError``, from ``backward()`` for the first two):
-``depth > 1``, frames whose padded height or width is odd, ``proj`` other than ``non_neg``.
+``depth > 1``, frames whose padded height or width is odd, ``proj`` other than ``non_neg``.  Inference takes any ``proj``:
+``forward()`` without gradients then runs every iteration split at the projection (lpc_iterate_begin / lpc_iterate_end),
+with the schedule's step and momentum factor of that iteration.
 
 The PSF is an autograd input as well: ``forward(batch, psfs=p)`` with ``p.requires_grad``, or a ``p`` set earlier through
 ``_set_psf(p)``, gets ``dL/dp`` in ``p``'s shape, dtype and device from the same reverse sweep (the engine still works on

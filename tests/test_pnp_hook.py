@@ -95,6 +95,23 @@ def test_split_protocol_errors(backend):
     adm = lpa.ADMM(psf)
     with pytest.raises(NativeError):
         adm._handle.iterate_begin()
+    # a handle with an unrolled schedule takes split iterations too: begin + non_neg + end == the fused iteration with that
+    # iteration's step and momentum factor (the second one: factor 0.3 on x_k - x_{k-1})
+    fis = [lpa.FISTA(psf) for _ in range(2)]
+    for f in fis:
+        f.set_data(rec._data)
+        f._handle.set_fista_schedule([[0.5], [0.25]], [0.0, 0.3], 0)
+        f.reset()
+    fis[0]._iterate(2)
+    fis[1]._iterate(1)
+    h = fis[1]._handle
+    h.iterate_begin()
+    h.get_state("image_est", x.data_ptr())
+    proj = torch.clamp(x, min=0).contiguous()
+    h.iterate_end(proj.data_ptr())
+    want = fis[0]._image_est
+    assert float(np.abs(np.asarray(want)).max()) > 0 and rel(fis[1]._image_est, want) <= 2e-6
+    assert rel(fis[1]._image_est, lpa.FISTA(psf)._image_est) > 1e-3        # (and it moved)
 
 
 def pnp_denoise(x, noise_level):          # the function the golden generator handed to the reference

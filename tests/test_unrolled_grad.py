@@ -240,13 +240,21 @@ def test_refusals(backend):
     with pytest.raises(RuntimeError, match="tape overwritten"):
         first.sum().backward()
     forward_only_works(rec, data, first)
-    # a custom projection: the engine has never run it together with an unrolled schedule (lpc_iterate_begin refuses);
-    # with gradients asked for the refusal is a NotImplementedError
+    # a custom projection is not differentiated: with gradients asked for the refusal is a NotImplementedError; without
+    # them it runs as split iterations on the schedule (tests/test_hooks_over_plans.py has the parity) -- here non_neg in
+    # disguise against the fused forward -- and a handle that is writing its tape refuses a split iteration itself
     rec, data = solver(10, 12, proj=lambda x: torch.clamp(x, min=0.0))
     with pytest.raises(NotImplementedError, match="non_neg"):
         rec(data)
-    with torch.no_grad(), pytest.raises(_native.NativeError, match="unrolled schedule"):
-        rec(data)
+    with torch.no_grad():
+        hooked = rec(data)
+    fused = lpa.UnrolledFISTA(rec._psf, n_iter=3)
+    with torch.no_grad():
+        want = fused(data)
+    assert float(want.abs().max()) > 0 and rel(hooked, want) <= 2e-6
+    fused(data)                                               # (the parameters require gradients: this forward records)
+    with pytest.raises(_native.NativeError, match="records a tape"):
+        fused._handle.iterate_begin()
     # raw ABI: a FISTA handle without a schedule
     fis = lpa.FISTA(torch.from_numpy(rng.random((1, 10, 12, 3)).astype(np.float32)).to(dev))
     buf = torch.zeros(2 * 10 * 12 * 3, dtype=torch.float32, device=dev)

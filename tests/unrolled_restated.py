@@ -54,11 +54,13 @@ def default_steps(psf, n, tk0=1.0):
     return np.tile(a0.numpy().astype(np.float32), (n, 1)), np.asarray(tks, dtype=np.float32)
 
 
-def restated(psf, data, alpha_p, tk_p, n, init=None, dtype=torch.float64):
+def restated(psf, data, alpha_p, tk_p, n, init=None, dtype=torch.float64, proj=None):
     """the five formula lines of the forward iteration in torch.fft, in ``dtype`` (t_k and the momentum factor in float32
     like unrolled_fista.py:104), for torch.autograd.  ``data`` may have one channel against a three-channel PSF (the
-    broadcast of ``- self._data``).  Returns the output and, detached, every argument of the projection:
-    z_0 .. z_{n-1} and y_n."""
+    broadcast of ``- self._data``).  ``proj``: the projection (unrolled_fista.py:104 and the read-out, :80-81); None is
+    non-negativity.  Returns the output and, detached, every argument of the projection: z_0 .. z_{n-1} and y_n."""
+    if proj is None:
+        proj = lambda v: torch.clamp(v, min=0)  # noqa: E731
     psf, data = psf.to(dtype), data.to(dtype)
     D, H, W, C = psf.shape
     pad, (Hp, Wp, sh, sw), Hs = _spectrum(psf, dtype)
@@ -77,12 +79,12 @@ def restated(psf, data, alpha_p, tk_p, n, init=None, dtype=torch.float64):
     args = []
     for i in range(n):
         z = y - a[i] * conv(conv(y, False) - data, True)
-        xn = torch.clamp(z, min=0)
+        xn = proj(z)
         y = xn + ((t[i] - 1) / t[i + 1]) * (xn - xk)
         xk = xn
         args.append(z.detach())
     args.append(y.detach())
-    return torch.clamp(y, min=0), args
+    return proj(y), args
 
 
 PLANS = {"rows_half": ({"rows_half": 1}, "reverse rows: half-length, run-time plan"),
