@@ -112,6 +112,9 @@ typedef struct lpc_config {
  *                      stored; rows of up to 1024 points then run on 256 lanes at every batch size)
  *   k1_group=N         ... on launches of more than 8192 row blocks: runs of N consecutive blocks per XCD (default 16;
  *                      0: launch order)
+ *   admm_rows_v2=BITS  the second form of the half-length row kernels (lpc_admm_v2_kernels.h; wherever the row plan has one
+ *                      radix and the window offset / width are even; float32; same bits as the first form): 1 the forward
+ *                      rows with the X half (default), 2 the inverse rows (slower at 12 MP), 3 both; 0: first form
  * Block orders (permutations)
  *   rev_order=BITS     which ADMM kernels walk their grids backwards (1 tiled kernel, 2 / 4 forward / inverse pass A,
  *                      8 LDS middle; default 9);  gd_rev=BITS (gradient-descent family / operator: 1 residual rows, 2

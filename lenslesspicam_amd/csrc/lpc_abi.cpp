@@ -439,6 +439,9 @@ int lpc_plan_info(lpc_handle e, char* buf, size_t n) {
   const bool rows_static = e->mod && sp.row_kind && (pl.rows_half || e->cfg.algo == LPC_ALGO_ADMM);
   if (rows_static) s += " [static " + rad_list(sp.row, ".") + ", " + std::to_string(sp.row.nt) + " threads]";
   if (pl.gd_v2) s += " (fused rows: second form, " + std::to_string(sp.row.n / sp.row.rad[0]) + " lanes)";
+  if (pl.admm_rows_v2)
+    s += std::string(" (ADMM rows: second form, ") + (pl.admm_rows_v2 == 3 ? "forward + inverse, " : pl.admm_rows_v2 == 2 ? "inverse, " : "forward, ") +
+         std::to_string(sp.row.n / sp.row.rad[0]) + " lanes)";
   s += "; columns: " + (pl.N1 > 1 ? std::to_string(pl.N1) + " x " + std::to_string(pl.N2) + " split" : std::string("single pass ") + std::to_string(pl.N2));
   s += ", T = " + std::to_string(pl.T);
   if (e->mod && sp.passA.n) s += ", pass A [static " + rad_list(sp.passA, ".") + ", T = " + std::to_string(sp.passA.T) + "]";

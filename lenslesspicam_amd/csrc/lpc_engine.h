@@ -115,6 +115,8 @@ struct LaunchPlan {
   bool k1_half = false;    // duals half-applied between the iterations of one call (AdmmScalars::half_in)
   bool rho_rsp = false;    // ... rho~ recovered from r_sp by the tiled TV / W kernel: rho not moved inside a call (AdmmScalars::rho_rsp)
   bool xi_half = false;    // ... xi half-applied too: the X half does not read H V_old where xi lives (AdmmScalars::xi_in)
+  int admm_rows_v2 = 0;    // half-length rows in their second form (lpc_admm_v2_kernels.h; option admm_rows_v2): bit 0 the
+                           // forward rows with the X half, bit 1 the inverse rows
   int k1_xcd_order = 0;    // K1Rows::xcd_order
   AdmmMid admm_mid = ADMM_MID_RT_LDS;
   int conv_mid_reg = 0;    // convolution middle (conv_middle) in registers: its pass-B length; 0: in LDS
@@ -398,6 +400,7 @@ struct LpcModule {
   int mid_pc;     // its sequential middle reads the precombined constants (AdmmState::midc / midrd)
   int slay;       // its ADMM row kernels and fused middle keep the work spectra in pair lines (PlanSpec::slay)
   int gd_v2;      // the module holds k_gd_resid_v2 / k_gd_update_fwd_v2 for its row plan (lpc_gd_v2_kernels.h)
+  int admm_rows_v2;   // ... k_rinv_half_v2 / k_rfwd_half_x_v2 (lpc_admm_v2_kernels.h)
 };
 // lpc_jit.cpp: the module of `spec` -- from the process cache, from disk, or (allow_compile) compiled now; null + `why`
 const LpcModule* get_plan_module(const PlanSpec& spec, const EngineOpts& opt, bool allow_compile, std::string* why);

@@ -1680,36 +1680,59 @@ static __device__ __forceinline__ XQuad xhalf_load(const PlaneGeom& g, const Adm
 }
 // xin: the updated xi -- half-applied, -a, with p.xi_out -- (stored by the caller unless c.skip && !p.xi_store);
 // as: a = mu1 X - xi'
+// One pixel (the per-element body of the quad form below and of the pair form of lpc_admm_v2_kernels.h): hv, ho = H V,
+// H V_old; xiv: the stored xi; yv: the measurement (0 outside the window); in: the pixel lies inside the sensor window.
+// Both results are assigned exactly once, at the end (profiles/dual_elision_notes.md: written any other way the callers'
+// arrays go to scratch).
+struct XElem { real xi, a; };
+static __device__ __forceinline__ XElem xhalf_elem(const AdmmScalars& p, real hv, real xiv, real ho, real yv, bool in) {
+  real a;
+  // outside the window: a = mu1 HV, xi = mu1p (HV - HV_old) -- stored on request only (xi_store).  In a quad that
+  // straddles the window's edge these lanes are stored with the quad in every iteration, and with xi_in H V_old is not
+  // loaded (ho = 0): between the iterations of a call they hold GARBAGE.  Nothing reads them (this branch never reads
+  // xi) until the last iteration, which loads H V_old and rewrites them.
+  if (p.xiw && !in) {
+    xiv = p.first ? (real)0. : p.mu1p * (hv - ho);
+    a = p.mu1 * hv;
+  } else {
+    if (!p.first) {
+      if (p.xi_in) {
+        xiv = xiv + p.mu1p * hv;                   // stored: xi' - mu1p X_old (AdmmScalars::xi_in)
+      } else {
+        const real xo = (in ? p.m_in_p : p.m_out_p) * (xiv + p.mu1p * ho + yv);   // previous X
+        xiv = xiv + p.mu1p * (hv - xo);
+      }
+    }
+    const real xnew = (in ? p.m_in : p.m_out) * (xiv + p.mu1 * hv + yv);
+    a = p.mu1 * xnew - xiv;
+    if (p.xi_out) xiv = -a;
+  }
+  XElem r;
+  r.xi = xiv;
+  r.a = a;
+  return r;
+}
 static __device__ __forceinline__ void xhalf_apply(const AdmmScalars& p, const XQuad& c, real xin[4], real as[4]) {
   const real hvs[4] = {c.hv.x, c.hv.y, c.hv.z, c.hv.w}, xis[4] = {c.xi.x, c.xi.y, c.xi.z, c.xi.w};
   const real hos[4] = {c.ho.x, c.ho.y, c.ho.z, c.ho.w};
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    real xiv = xis[i], a;
-    const real hv = hvs[i], yv = c.ys[i];
-    // outside the window: a = mu1 HV, xi = mu1p (HV - HV_old) -- stored on request only (xi_store).  In a quad that
-    // straddles the window's edge these lanes are stored with the quad in every iteration, and with xi_in H V_old is not
-    // loaded (hos = 0): between the iterations of a call they hold GARBAGE.  Nothing reads them (this branch never reads
-    // xi) until the last iteration, which loads H V_old and rewrites them.
-    if (p.xiw && !c.ins[i]) {
-      xiv = p.first ? (real)0. : p.mu1p * (hv - hos[i]);
-      a = p.mu1 * hv;
-    } else {
-      if (!p.first) {
-        if (p.xi_in) {
-          xiv = xiv + p.mu1p * hv;                   // stored: xi' - mu1p X_old (AdmmScalars::xi_in)
-        } else {
-          const real xo = (c.ins[i] ? p.m_in_p : p.m_out_p) * (xiv + p.mu1p * hos[i] + yv);   // previous X
-          xiv = xiv + p.mu1p * (hv - xo);
-        }
-      }
-      const real xnew = (c.ins[i] ? p.m_in : p.m_out) * (xiv + p.mu1 * hv + yv);
-      a = p.mu1 * xnew - xiv;
-      if (p.xi_out) xiv = -a;
-    }
-    xin[i] = xiv;
-    as[i] = a;
+    const XElem r = xhalf_elem(p, hvs[i], xis[i], hos[i], c.ys[i], c.ins[i]);
+    xin[i] = r.xi;
+    as[i] = r.a;
   }
+}
+// the same on the two pixels of one pair (no H V_old: the steady state of a call, xi_in without xi_store): xa = (xi, xi),
+// as = (a, a) of columns 2 i, 2 i + 1, which lie both inside or both outside the window (pair geometry).
+// ho: the zero that stands for the H V_old the quad form did not load, as a value the compiler cannot see through
+// (lpc_opaque_f) -- with a literal 0 it merges mu1p (hv - 0) of the branch outside the window with the mu1p hv inside
+// xi + mu1p hv of the other branch into one product with two uses, which then is no longer contracted into an FMA: the
+// quad form's xi' and this one's differed by a rounding (profiles/admm_rows_v2_notes.md)
+static __device__ __forceinline__ void xhalf_apply2(const AdmmScalars& p, real2 hv, real2 xi, real2 y, bool in, real ho,
+                                                    real2& xin, real2& as) {
+  const XElem r0 = xhalf_elem(p, hv.x, xi.x, ho, y.x, in), r1 = xhalf_elem(p, hv.y, xi.y, ho, y.y, in);
+  xin = make_real2(r0.xi, r1.xi);
+  as = make_real2(r0.a, r1.a);
 }
 
 // ---- forward rows of r_sp and a, with the X half of the image-domain work (wide frames: one real row per half-length

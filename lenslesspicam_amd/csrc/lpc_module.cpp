@@ -8,6 +8,7 @@
 #include "lpc_gd_launch.h"
 #include "lpc_gd_bwd_launch.h"
 #include "lpc_gd_v2_kernels.h"
+#include "lpc_admm_v2_kernels.h"
 
 #ifndef LPC_MOD_MID_PRE
 #define LPC_MOD_MID_PRE 0
@@ -45,13 +46,44 @@ static int m_rows_inv_single(Engine* e, const real2* S, const RealDst* dst, int 
   return launch_rows_inv_half<RNT, REM, RSK>(e, row_arg(e), S, *dst, nplanes, kid);
 }
 #if LPC_MOD_FAMILY == LPC_FAM_ADMM
+// the second form of the two row kernels (lpc_admm_v2_kernels.h; LaunchPlan::admm_rows_v2): one-radix plan, M / R lanes per
+// row, the tile in the natural layout like the gradient-descent family's second form
+#ifndef LPC_MOD_V2_SK
+#define LPC_MOD_V2_SK LPC_LAY_NONE
+#endif
+static constexpr int V2SK = LPC_MOD_V2_SK;
+static const size_t kV2Smem = LPC_ROW_SMEM_BYTES(RowP::n, V2SK);
 static int m_admm_rows_fwd(Engine* e) { return launch_admm_rows_fwd_half<RNT, REM, RSK>(e, row_arg(e)); }
 static int m_admm_rows_inv(Engine* e, real* Vout, real* HVout, int skip_hv_outside) {
+#ifndef LPC_DOUBLE
+  if constexpr (GdV2<RowP>::ok) {
+    if (e->plan.admm_rows_v2 & 2) {
+      const PlaneGeom& g = e->g;
+      constexpr int NB = GdV2<RowP>::NB;
+      return launch_k(e, LPC_K_ROW_INV, k_rinv_half_v2<NB, V2SK, RowPA>, dim3(skip_hv_outside ? g.Hp + g.H : 2 * g.Hp, e->P), NB,
+                      kV2Smem, g, row_arg(e), (const real2*)e->planW.tw, (const real2*)e->S, (const real2*)spec_b(e), Vout,
+                      HVout, skip_hv_outside ? 1 : 0);
+    }
+  }
+#endif
   return launch_admm_rows_inv_half<RNT, REM, RSK>(e, row_arg(e), Vout, HVout, skip_hv_outside != 0);
 }
 #if LPC_MOD_ROW_X
 static int m_admm_rows_fwd_x(Engine* e, const AdmmScalars* sc, const K1Rows* k1) {
   if (k1) return fail("internal: half-length rows do not hold the TV / W half");
+#ifndef LPC_DOUBLE
+  if constexpr (GdV2<RowP>::ok) {
+    // the steady state of a call: xi half-applied on both sides, H V_old not read (xhalf_load); the first and the last
+    // iteration of a call keep the first form -- the two agree bit for bit
+    if ((e->plan.admm_rows_v2 & 1) && !sc->first && sc->xi_in && sc->xi_out && !(sc->xiw && sc->xi_store)) {
+      constexpr int NB = GdV2<RowP>::NB;
+      return launch_k(e, LPC_K_ROW_FWD, k_rfwd_half_x_v2<NB, V2SK, RowPA>, dim3(2 * e->g.Hp, e->P), NB, kV2Smem, e->g, *sc,
+                      row_arg(e), (const real2*)e->planW.tw, (const real*)e->admm.Rsp, (const real*)e->admm.HVb[e->admm.hcur],
+                      e->admm.xi, (const real*)e->Y, e->S, spec_b(e), make_fastdiv((unsigned)e->g.DC),
+                      make_fastdiv((unsigned)e->g.C));
+    }
+  }
+#endif
   return launch_k(e, LPC_K_ROW_FWD, k_rfwd_half_x<RNT, REM, RSK, RowPA>, dim3(2 * e->g.Hp, e->P), RNT, kRowSmem,
                   e->g, *sc,
                   row_arg(e), (const real2*)e->planW.tw, (const real*)e->admm.Rsp, (const real*)e->admm.HVb[e->admm.hcur],
@@ -195,6 +227,9 @@ extern "C" int lpc_module_init(LpcModule* m, size_t engine_size, const char* src
 #if LPC_MOD_ROW_KIND != 0 && LPC_MOD_FAMILY == LPC_FAM_ADMM
   m->admm_rows_fwd = m_admm_rows_fwd;
   m->admm_rows_inv = m_admm_rows_inv;
+#if LPC_MOD_ROW_KIND == LPC_ROWS_HALF && !defined(LPC_DOUBLE)
+  m->admm_rows_v2 = GdV2<RowP>::ok ? 1 : 0;
+#endif
 #if LPC_MOD_ROW_X
   m->admm_rows_fwd_x = m_admm_rows_fwd_x;
 #if LPC_MOD_ROW_KIND == LPC_ROWS_PAIRED

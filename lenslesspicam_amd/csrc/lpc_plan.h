@@ -143,6 +143,8 @@ struct EngineOpts {
   int k1_half = 1;            // duals half-applied between the iterations of one call: the tiled kernel does not read V_old
   int rho_rsp = 1;            // ... and reads rho~ back out of r_sp: rho is not moved between the iterations of a call
   int xi_half = 1;            // ... xi half-applied as well: the X half of the forward rows does not read H V_old inside the window
+  int admm_rows_v2 = 1;       // half-length rows on a one-radix plan, second form (lpc_admm_v2_kernels.h): bit 0 the forward rows
+                              // with the X half, bit 1 the inverse rows (measured slower at 12 MP: off by default); 0: first form
   // -- block orders (permutations: results unchanged)
   int rev_order = 9;          // bit 0 / 1 / 2 / 3: the tiled ADMM kernel / forward pass A / inverse pass A / the LDS middle walk
                               // their grids BACKWARDS: a kernel that starts where its predecessor finished finds the last
@@ -207,6 +209,7 @@ static inline std::string parse_engine_opts(const char* str, EngineOpts& o) {
       else if (k == "k1_half") o.k1_half = (int)iv;
       else if (k == "rho_rsp") o.rho_rsp = (int)iv;
       else if (k == "xi_half") o.xi_half = (int)iv;
+      else if (k == "admm_rows_v2") o.admm_rows_v2 = (int)iv;
       else if (k == "mid_pc") o.mid_pc = (int)iv;
       else if (k == "rev_order") o.rev_order = (int)iv;
       else if (k == "gd_rev") o.gd_rev = (int)iv;

@@ -338,6 +338,11 @@ void finish_plan(const lpc_config& c, const EngineOpts& o, const PlaneGeom& g, i
   // xi_half=0: off; k1_half=0 implies both off)
   pl.rho_rsp = pl.k1_half && pl.k1 == ADMM_K1_TV_W && o.rho_rsp != 0;
   pl.xi_half = pl.k1_half && o.xi_half != 0;
+  // the second form of the half-length row kernels (one-radix row plan, float32: the module says so); the blocks of `a` make
+  // 8-byte accesses to y and xi: even window offset and frame width
+  // (bit 0: the forward rows -- the default; bit 1: the inverse rows as well, slower at 12 MP: profiles/admm_rows_v2_notes.md)
+  pl.admm_rows_v2 = (admm && pl.rows_half && mod && mod->admm_rows_v2 && lane_twiddles && ((g.sw | g.W) & 1) == 0 && g.W >= 2)
+                        ? (o.admm_rows_v2 & 3) : 0;
   // K1Rows::xcd_order.  (The XCD-aware block orders assume the MI355X's 8 XCDs x 32 CUs and its dispatch rule "workgroup w
   // on XCD w % 8"; any other part gets launch order: the orders are permutations, results are the same.)
   pl.k1_xcd_order = cu != 256 ? 0 : (long)paired_rows_grid(g, false) * P <= 8192 ? -1 : std::max(0, o.k1_group);

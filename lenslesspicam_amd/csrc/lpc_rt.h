@@ -59,6 +59,7 @@ static inline unsigned __umulhi(unsigned a, unsigned b) { return (unsigned)(((ui
 struct lpc_rsrc { char* base; unsigned bytes; };
 static inline lpc_rsrc lpc_make_rsrc(const void* base, unsigned bytes) { lpc_rsrc r; r.base = (char*)base; r.bytes = bytes; return r; }
 static inline int lpc_opaque(int x) { return x; }
+static inline float lpc_opaque_f(float x) { return x; }
 #define LPC_SCHED_FENCE() ((void)0)
 
 typedef void* lpcStream_t;
@@ -153,6 +154,8 @@ static __device__ __forceinline__ lpc_rsrc lpc_make_rsrc(const void* base, unsig
   return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);   // gfx9: DATA_FORMAT = 32 bit
 }
 static __device__ __forceinline__ int lpc_opaque(int x) { asm volatile("" : "+v"(x)); return x; }
+// (a float the optimiser knows nothing about: keeps a constant operand from merging two statements into one)
+static __device__ __forceinline__ float lpc_opaque_f(float x) { asm volatile("" : "+s"(x)); return x; }    // wave-uniform: stays scalar
 // nothing is scheduled across this point (keeps a batch of loads behind the arithmetic whose registers it needs)
 #define LPC_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 typedef hipStream_t lpcStream_t;
