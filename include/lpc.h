@@ -154,6 +154,26 @@ int lpc_padded_shape(lpc_handle h, int* Hp, int* Wp, int* start_h, int* start_w)
  * the step alpha and the default initial estimate).  rfft_convolve.py:102-131,
  * admm.py:186-193, gd.py:94-126.  Implies lpc_reset(). */
 int lpc_set_psf(lpc_handle h, const lpc_real* dev_psf, void* stream);
+/* One PSF per frame: dev_psfs is (cfg.batch, D, H, W, C), and frame b of every later call is convolved with PSF b
+ * (trainable_recon.py:346-350 rebuilds its convolver from a 5-D `psfs`, rfft_convolve.py:55-58,84-117).  The handle then
+ * holds batch*D*C PSF spectra instead of D*C -- state plane q reads plane q where it read q % (D*C) -- until the next
+ * lpc_set_psf, which returns to one PSF for the batch.  Like lpc_set_psf it implies lpc_reset(), and ADMM's precombined
+ * middle constants are remade at the next iteration; unlike lpc_set_psf it leaves a caller's gram (lpc_set_psi_gram) in
+ * place -- the gram of the prior does not depend on the PSF.  One launch sequence for all the PSFs (layout, forward transform of
+ * batch*D*C planes, norm scale, pair-line copy); it does not wait for the stream, except at the first call of a handle,
+ * which gives the D*C-plane buffers back and allocates them for batch*D*C planes:
+ *     workspace_bytes grows by (batch - 1) * D*C * (spectrum plane + frame), for ADMM handles whose plan keeps pair-line
+ *     copies by another spectrum plane, and with the sequential middle's precombined constants by 1.5 (real phases) or 2.5
+ *     (complex phases) more.  (Spectrum plane: 2 * sizeof(real) * ((Hp + 1) & ~1) * cpitch bytes, cpitch = Wp/2 + 1 rounded
+ *     up to 16; frame: sizeof(real) * H * W.)  The buffers keep that size for the life of the handle.
+ * lpc_iterate, lpc_form_image, lpc_get_state, the plug-and-play and custom-psi steps, lpc_convolve,
+ * lpc_convolve_spectrum (n == cfg.batch: plane q of the input meets PSF plane q) and lpc_reconstruction_error work as
+ * before.  Refused, with a message that says "per-frame":
+ *     lpc_fista_record / lpc_admm_record with a non-zero argument, the four backward entries, and this call on a handle
+ *     that records: gradients with per-frame PSFs are not implemented;
+ *     a gradient-descent handle without a pinned start value (lpc_set_start_value) and a schedule
+ *     (lpc_set_fista_schedule): plain GD / Nesterov / FISTA take their step and start value from ONE PSF. */
+int lpc_set_psf_batch(lpc_handle h, const lpc_real* dev_psfs, void* stream);
 
 /* out = ifftshift(irfft2(rfft2(pad?(x)) * H or conj(H))) cropped if cfg.pad.
  * x: (n, D, Hx, Wx, x_channels), out: (n, D, Hx, Wx, C) with (Hx,Wx) = (H,W) if cfg.pad else (Hp,Wp);

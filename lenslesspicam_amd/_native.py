@@ -111,6 +111,7 @@ class Lib:
             "lpc_plan_module": [C.POINTER(Config), C.c_int, C.c_char_p, C.c_size_t],
             "lpc_padded_shape": [vp, ip, ip, ip, ip],
             "lpc_set_psf": [vp, fp, vp],
+            "lpc_set_psf_batch": [vp, fp, vp],
             "lpc_convolve": [vp, fp, fp, C.c_int, C.c_int, C.c_int, vp],
             "lpc_convolve_spectrum": [vp, fp, fp, C.c_int, C.c_int, C.c_int, vp],
             "lpc_set_data": [vp, fp, C.c_int, vp],
@@ -241,6 +242,10 @@ class Handle:
 
     def set_psf(self, ptr, stream=0):
         self._c(self.lib.dll.lpc_set_psf(self.h, ptr, stream))
+
+    def set_psf_batch(self, ptr, stream=0):
+        """one PSF per frame: ``ptr`` holds (batch, D, H, W, C) values (lpc_set_psf_batch); ``set_psf`` returns to one"""
+        self._c(self.lib.dll.lpc_set_psf_batch(self.h, ptr, stream))
 
     def convolve(self, x_ptr, out_ptr, n, x_channels, adjoint, stream=0):
         self._c(self.lib.dll.lpc_convolve(self.h, x_ptr, out_ptr, n, int(x_channels), int(adjoint), stream))

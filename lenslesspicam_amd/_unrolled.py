@@ -60,9 +60,28 @@ class _Taped:
         assert isinstance(batch, torch.Tensor) and len(batch.shape) == 5, "batch must be of shape (N, D, H, W, C)"
         if background is not None:
             raise NotImplementedError("background subtraction networks are outside the hot path")
-        if isinstance(psfs, torch.Tensor) and psfs.dim() == 5:
-            raise NotImplementedError(f"{self._solver}: per-frame PSFs (a 5-D psfs) are not implemented: one PSF for the "
-                                      "batch")
+
+    def _per_frame(self, psfs):
+        """is ``psfs`` one PSF per measurement, (B, D, H, W, C)?"""
+        return isinstance(psfs, torch.Tensor) and psfs.dim() == 5
+
+    def _refuse_per_frame_training(self, psfs):
+        """a forward that records, once ``train`` is known: per-frame PSFs -- handed in now, or current since an earlier
+        forward -- are inference only"""
+        if self._per_frame(psfs) or self._psfs is not None:
+            raise NotImplementedError(f"{self._solver}: gradients with per-frame PSFs (a 5-D psfs) are not implemented: "
+                                      "run such a batch under torch.no_grad(), or give one PSF for the batch")
+
+    def _take_psfs(self, batch, psfs):
+        """``psfs=`` of a forward that does not record: 4-D, one PSF for the batch (from now on); 5-D, one per measurement
+        (current for later batches of the same size, like the convolver the reference rebuilds and keeps)"""
+        if psfs is None:
+            return
+        if self._per_frame(psfs):
+            assert int(psfs.shape[0]) == int(batch.shape[0]), "psfs must hold one PSF per measurement: (B, D, H, W, C)"
+            self._set_psfs(psfs)
+        else:
+            self._set_psf(psfs)
 
 
 def _meta(t):

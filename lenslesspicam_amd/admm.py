@@ -20,6 +20,7 @@ from .recon import ReconstructionAlgorithm
 
 class ADMM(ReconstructionAlgorithm):
     _ALGO = _native.ALGO_ADMM
+    _PER_FRAME_PSFS = True      # nothing of ADMM but H itself follows the PSF (the gram of the prior does not)
 
     def __init__(self, psf, dtype=None, mu1=1e-6, mu2=1e-5, mu3=4e-5, tau=0.0001, psi=None, psi_adj=None,
                  psi_gram=None, pad=False, norm="backward", denoiser=None, **kwargs):

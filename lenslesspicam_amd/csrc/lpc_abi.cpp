@@ -112,6 +112,37 @@ int lpc_set_psf(lpc_handle e, const real* dev_psf, void* stream) {
   return 0;
 }
 
+// One PSF per frame (include/lpc.h).  What such a handle does not do names the reason with the word "per-frame"
+static int per_frame_refusal(const Engine* e, const char* who) {
+  if (!e->psf_per_frame) return 0;
+  return fail(std::string(who) + ": not available with per-frame PSFs (lpc_set_psf_batch): their gradients are not implemented");
+}
+// the gradient-descent family takes its step and its default start value from ONE PSF (gd.py:100-112): with one PSF per
+// frame both must come from the caller -- unrolled FISTA's schedule and pinned start value (unrolled_fista.py:57-72)
+static int per_frame_gd_check(const Engine* e, const char* who) {
+  if (e->cfg.algo < LPC_ALGO_GD || (e->gd.gx0_pinned && e->fista.sched_n > 0)) return 0;
+  return fail(std::string(who) + ": per-frame PSFs need a pinned start value (lpc_set_start_value) and a schedule "
+              "(lpc_set_fista_schedule) on a gradient-descent handle: plain iterations take their step and start value from one PSF");
+}
+
+int lpc_set_psf_batch(lpc_handle e, const real* dev_psfs, void* stream) {
+  if (!e || !dev_psfs) return fail("lpc_set_psf_batch: null argument");
+  LPC_OK(per_frame_gd_check(e, "lpc_set_psf_batch"));
+  if (e->fista_tape.rec_on || e->admm_tape.rec_on)
+    return fail("lpc_set_psf_batch: the handle records a tape, and gradients with per-frame PSFs are not implemented");
+  e->stream = (lpcStream_t)stream;
+  // |PsiT Psi| does not depend on the PSF: the finite-difference gram is made by the first PSF a handle gets, and a
+  // caller's gram (lpc_set_psi_gram) stays; otherwise nothing here waits for the stream
+  const bool gram = e->cfg.algo == LPC_ALGO_ADMM && !e->psf_set;
+  LPC_OK(set_psf_batch(e, dev_psfs));
+  e->admm.midc_valid = false;
+  e->fista_tape.invalidate();
+  e->admm_tape.invalidate();
+  if (gram) LPC_OK(admm_setup_constants(e));
+  if (e->cfg.algo != LPC_ALGO_CONV) return lpc_reset(e, stream);
+  return 0;
+}
+
 int lpc_convolve(lpc_handle e, const real* dev_x, real* dev_out, int n, int x_channels, int adjoint, void* stream) {
   if (!e || !dev_x || !dev_out) return fail("lpc_convolve: null argument");
   LPC_OK(check_channels(e, x_channels, "lpc_convolve"));
@@ -214,6 +245,7 @@ int lpc_set_fista_schedule(lpc_handle e, int n, const real* alpha, const real* c
 int lpc_fista_record(lpc_handle e, int on) {
   if (!e) return fail("null handle");
   if (e->cfg.algo != LPC_ALGO_FISTA) return fail("lpc_fista_record: not a FISTA handle");
+  if (on) LPC_OK(per_frame_refusal(e, "lpc_fista_record"));
   return tape_record(e, e->fista_tape, on, gd_tape_alloc);
 }
 
@@ -232,6 +264,7 @@ static int fista_backward(lpc_handle e, const real* dev_grad_out, real* dev_grad
                           real* dev_grad_coef, real* dev_grad_init, real* dev_grad_psf, void* stream) {
   if (!e || !dev_grad_out || !dev_grad_alpha || !dev_grad_coef) return fail("lpc_fista_backward: null argument");
   if (e->cfg.algo != LPC_ALGO_FISTA) return fail("lpc_fista_backward: not a FISTA handle");
+  LPC_OK(per_frame_refusal(e, "lpc_fista_backward"));
   if (e->fista.sched_n <= 0) return fail("lpc_fista_backward: the handle has no schedule (lpc_set_fista_schedule)");
   LPC_OK(tape_refusal(e, e->fista_tape, e->fista.sched_n, "fista", false));
   if (e->gd.split_pending) return fail("lpc_fista_backward: a split iteration is in flight (lpc_iterate_end missing)");
@@ -259,6 +292,7 @@ int lpc_fista_backward_psf(lpc_handle e, const real* dev_grad_out, real* dev_gra
 int lpc_admm_record(lpc_handle e, int on) {
   if (!e) return fail("null handle");
   if (e->cfg.algo != LPC_ALGO_ADMM) return fail("lpc_admm_record: not an ADMM handle");
+  if (on) LPC_OK(per_frame_refusal(e, "lpc_admm_record"));
   return tape_record(e, e->admm_tape, on, admm_tape_alloc);
 }
 
@@ -267,6 +301,7 @@ static int admm_backward_checked(lpc_handle e, const real* dev_grad_out, real* d
   if (!e || !dev_grad_out || !dev_grad_mu1 || !dev_grad_mu2 || !dev_grad_mu3 || !dev_grad_tau)
     return fail("lpc_admm_backward: null argument");
   if (e->cfg.algo != LPC_ALGO_ADMM) return fail("lpc_admm_backward: not an ADMM handle");
+  LPC_OK(per_frame_refusal(e, "lpc_admm_backward"));
   const long n = (long)e->admm.sched[0].size();
   if (n <= 0) return fail("lpc_admm_backward: the handle has no schedule (lpc_set_admm_schedule)");
   if (e->cfg.depth > 1) return fail("lpc_admm_backward: depth > 1 is not implemented");
@@ -305,6 +340,7 @@ int lpc_iterate(lpc_handle e, int n_iter, void* stream) {
   e->stream = (lpcStream_t)stream;
   if (e->gd.split_pending) return fail("lpc_iterate: a split iteration is in flight (lpc_iterate_end missing)");
   if (e->admm.pnp_mode) return fail("lpc_iterate: the handle runs plug-and-play iterations since the last reset");
+  if (e->psf_per_frame) LPC_OK(per_frame_gd_check(e, "lpc_iterate"));
   if (e->cfg.algo == LPC_ALGO_ADMM) return admm_iterate(e, n_iter);
   if (e->cfg.algo >= LPC_ALGO_GD) return gd_iterate(e, n_iter);
   return fail("lpc_iterate: operator-only handle");
@@ -317,6 +353,7 @@ int lpc_iterate_begin(lpc_handle e, void* stream) {
   if (!e->psf_set) return fail("lpc_iterate_begin: PSF not set");
   if (!e->data_set) return fail("Must set data with `set_data()`");
   if (e->gd.split_pending) return fail("lpc_iterate_begin: the previous split iteration was not finished");
+  if (e->psf_per_frame) LPC_OK(per_frame_gd_check(e, "lpc_iterate_begin"));
   if (e->fista_tape.rec_on)   // (the reverse sweep differentiates the fused projection only)
     return fail("lpc_iterate_begin: not available while the handle records a tape (lpc_fista_record)");
   e->stream = (lpcStream_t)stream;

@@ -40,6 +40,24 @@ static AdmmScalars admm_scalars(const Engine* e, const double cur[4]) {
   return p;
 }
 
+// what ADMM keeps per PSF plane besides Hs: the pair-line copy of H and the sequential middle's precombined constants.
+// Gives back what the handle holds of them first (lpc_set_psf_batch grows them from D*C to batch*D*C planes)
+int admm_alloc_psf(Engine* e, int nplanes) {
+  const PlaneGeom& g = e->g;
+  dev_free(e, e->admm.Hs_t); dev_free(e, e->admm.midc); dev_free(e, e->admm.midrd);
+  e->admm.Hs_t = nullptr; e->admm.midc = nullptr; e->admm.midrd = nullptr;
+  e->admm.midc_valid = false;
+  if (!g.slay) return 0;
+  LPC_OK(dev_alloc(e, &e->admm.Hs_t, (size_t)g.cplane * nplanes));
+  if (e->mod && e->mod->mid_pc) {
+    real2* c = nullptr;
+    LPC_OK(dev_alloc(e, &c, (size_t)g.cplane * nplanes * (e->mod->mid_pc == 1 ? 2 : 1)));
+    e->admm.midc = c;
+    LPC_OK(dev_alloc(e, &e->admm.midrd, (size_t)g.cplane * nplanes));
+  }
+  return 0;
+}
+
 static const int kGsepBlocks = 512;
 int admm_alloc(Engine* e) {
   const PlaneGeom& g = e->g;
@@ -53,16 +71,8 @@ int admm_alloc(Engine* e) {
   real** bufs[] = {&e->admm.eta0[1], &e->admm.eta1[1], &e->admm.Rsp, &e->admm.Aarr};
   for (real** b : bufs) LPC_OK(dev_alloc(e, b, rp));
   LPC_OK(dev_alloc(e, &e->admm.Gabs, (size_t)g.cplane));
-  if (g.slay) {
-    LPC_OK(dev_alloc(e, &e->admm.Gabs_t, (size_t)g.cplane));
-    LPC_OK(dev_alloc(e, &e->admm.Hs_t, (size_t)g.cplane * e->Ppsf));
-    if (e->mod && e->mod->mid_pc) {
-      real2* c = nullptr;
-      LPC_OK(dev_alloc(e, &c, (size_t)g.cplane * e->Ppsf * (e->mod->mid_pc == 1 ? 2 : 1)));
-      e->admm.midc = c;
-      LPC_OK(dev_alloc(e, &e->admm.midrd, (size_t)g.cplane * e->Ppsf));
-    }
-  }
+  if (g.slay) LPC_OK(dev_alloc(e, &e->admm.Gabs_t, (size_t)g.cplane));
+  LPC_OK(admm_alloc_psf(e, e->Ppsf));
   LPC_OK(dev_alloc(e, &e->admm.Ga, (size_t)g.Hp));
   LPC_OK(dev_alloc(e, &e->admm.Gb, (size_t)g.cpitch));
   LPC_OK(dev_alloc(e, &e->admm.Gpart, (size_t)2 * kGsepBlocks));
@@ -420,5 +430,8 @@ double admm_model_bytes(const Engine* e) {
   const PlaneGeom& g = e->g;
   const double eb = (double)sizeof(real);
   const double R = eb * g.Hp * g.Wp * e->P, S = 2 * eb * g.Hp * g.Wc * e->P;
-  return 19.0 * R + eb * g.H * g.W * e->Pdata + 13.5 * S;
+  // one PSF per frame: every frame's middle reads spectral constants of its own (shared, they are read once per batch and
+  // stay out of the model)
+  const double Sc = e->psf_per_frame ? 2 * eb * g.Hp * g.Wc * e->Ppsf : 0.0;
+  return 19.0 * R + eb * g.H * g.W * e->Pdata + 13.5 * S + Sc;
 }

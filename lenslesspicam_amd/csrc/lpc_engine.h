@@ -230,7 +230,9 @@ struct lpc_engine : LaunchCtx {
   std::string mod_note;    // why there is no module, for lpc_plan_info
   bool rows_r2 = false; // row plans end in a radix-2 stage: fold it into the Hermitian (un)tangling
   ColPass passA{}, passB{};
-  int P = 0, Ppsf = 0, Pdata = 0;
+  int P = 0, Ppsf = 0, Pdata = 0;      // Ppsf: PSF planes in use = g.PM (DC, or P with one PSF per frame)
+  int psf_cap = 0;                      // ... and the planes Hs, psf_planar, Hs_t, midc and midrd have room for
+  bool psf_per_frame = false;           // lpc_set_psf_batch set the PSFs (until the next lpc_set_psf)
   std::vector<std::pair<void*, size_t>> allocs;   // every device allocation of the handle and its bytes (dev_alloc / dev_free)
   size_t total_bytes = 0;
 
@@ -426,6 +428,7 @@ int upload(Engine* e, void* dst, const void* src, size_t bytes);
 int setup_geometry(Engine* e);
 int alloc_common(Engine* e);                                    // PSF spectrum, work spectra, data / staging planes
 int set_psf(Engine* e, const real* dev_psf);
+int set_psf_batch(Engine* e, const real* dev_psfs);             // one PSF per frame: (B, D, H, W, C)
 int fft2_forward_setup(Engine* e, const RealSrc& src, real2* S, int nplanes);
 int cols_fwd_full(Engine* e, real2* S, int nplanes, int zr0, int zr1);   // row spectra (rows [zr0, zr1)) -> full 2-D spectra, Hs layout
 int convolve_planar(Engine* e, const real* xin, real* xout, int nplanes, bool padded_io, bool adjoint);
@@ -440,6 +443,7 @@ int fill_planar(Engine* e, real* p, long n, real v);
 int plane_minmax(Engine* e, const real2* Hs, const real* plane, int nblk, int nplanes, real* partial);   // k_plane_minmax
 // lpc_admm.cpp
 int admm_alloc(Engine* e);
+int admm_alloc_psf(Engine* e, int nplanes);                     // the copies of H and what is precombined from it, for nplanes PSF planes
 int admm_setup_constants(Engine* e);
 int admm_reset(Engine* e);
 int admm_iterate(Engine* e, int n_iter);

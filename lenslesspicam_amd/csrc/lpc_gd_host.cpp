@@ -188,5 +188,7 @@ int gd_kernel_bytes(Engine* e, int kid, double* bytes) {
 double gd_model_bytes(const Engine* e) {
   const PlaneGeom& g = e->g;
   const double eb = (double)sizeof(real), S = 2 * eb * g.Hp * g.Wc * e->P;
-  return (e->cfg.algo == LPC_ALGO_GD ? 6.0 : 8.0) * eb * g.H * g.W * e->P + 14.0 * S;
+  // one PSF per frame: each of the two middles reads a spectrum of H per state plane (shared: once per batch, not counted)
+  const double Sc = e->psf_per_frame ? 2 * eb * g.Hp * g.Wc * e->Ppsf : 0.0;
+  return (e->cfg.algo == LPC_ALGO_GD ? 6.0 : 8.0) * eb * g.H * g.W * e->P + 14.0 * S + 2.0 * Sc;
 }

@@ -25,13 +25,16 @@ struct PlaneGeom {
   long rplane;     // floats per padded real plane
   long cplane;     // real2 per spectrum plane
   long uplane;     // floats per un-padded plane
-  int DC;          // D*C: number of PSF planes (state plane q uses PSF plane q % DC)
+  int DC;          // D*C: planes of one frame
   int C;           // channels (data plane of state plane q = (q / DC) * C + q % C)
   int rev;         // per launch (the launcher sets it on its copy): the row kernels that honour it hand their workgroups
                    // out from the last (plane, row) to the first (see ColPass::rev)
   int slay;        // layout of the ADMM work spectra (and of the copies of H / |G| the fused middle reads): 0 rows of cpitch
                    // elements; 1 PAIR LINES (spec_col below) -- kernels take it as a template argument, the host and
                    // paired_rows_of read this copy
+  int PM;          // PSF planes the handle holds: state plane q uses PSF plane q % PM.  DC: one PSF for the batch
+                   // (lpc_set_psf); batch * DC: one PSF per frame (lpc_set_psf_batch), q % PM == q.  (Last, so that a
+                   // kernel that does not read it finds every other field where it was)
 };
 // ---- pair-line layout of a half spectrum (paired rows + 8-column middles: DiffuserCam-sized frames) --------------------
 // The single-pass fused middle of a 540-row frame holds 8 image columns per tile: 64-byte row segments, half a cache line
@@ -833,7 +836,7 @@ __global__ __launch_bounds__(64) void k_cols_mid_admm_reg(PlaneGeom g, Fft1dPlan
   const long urow = (long)row0 * g.cpitch;
   real2* ba = SA + (long)blockIdx.z * g.cplane + urow;
   real2* bb = SB + (long)blockIdx.z * g.cplane + urow;
-  const real2* hb = Hs + (long)((int)blockIdx.z % g.DC) * g.cplane + urow;
+  const real2* hb = Hs + (long)((int)blockIdx.z % g.PM) * g.cplane + urow;
   const real* gb = Gabs + urow;
   const bool gsep = cp.ga != nullptr;
   const real* gar = gsep ? cp.ga + row0 : Gabs;          // wave-uniform row terms (scalar loads, like the row phases)
@@ -920,7 +923,7 @@ __global__ __launch_bounds__(NT) void k_cols_mid_admm(PlaneGeom g, PL plan, ColP
   const long rowoff = ((long)grp * cp.gstride) * g.cpitch + (SL ? 2 * c0 : c0);      // (SL: single pass, grp == 0)
   real2* ba = SA + (long)by * g.cplane + rowoff;
   real2* bb = SB + (long)by * g.cplane + rowoff;
-  const int pp = (int)by % g.DC;
+  const int pp = (int)by % g.PM;
   const real2* hb = Hs + (long)pp * g.cplane + rowoff;
   const real* rb = Gabs + rowoff;  // |PsiT Psi| spectrum: one plane, the same for every channel
   const int npair = cp.N * T;
@@ -1085,11 +1088,13 @@ __global__ __launch_bounds__(NT, MINW) void k_cols_mid_admm_seq(PlaneGeom g, PL 
   // runs on XCD b % 8 -- consecutive blocks are the same column tile of the same PSF plane in different frames, so each
   // XCD's L2 fetches that tile of H / |G| from HBM once and serves it to the frames it owns.  (With the tile index
   // fastest, the 64 frames of C4 re-read H 64 times: PMC traffic 2.29 GB per launch against 1.60 GB algorithmic.)
-  const int nfr = (int)(gridDim.x / (unsigned)(cp.ntile_c * g.DC));       // frames
+  // (One PSF per frame, PlaneGeom::PM == all the planes: nfr == 1 and pp is the state plane itself -- nothing is shared
+  // between frames then, and the order is neutral)
+  const int nfr = (int)(gridDim.x / (unsigned)(cp.ntile_c * g.PM));       // frames (that share a PSF plane)
   const unsigned bx = cp.rev ? gridDim.x - 1u - blockIdx.x : blockIdx.x;   // ColPass::rev
   const int fr = (int)(bx % (unsigned)nfr), rest = (int)(bx / (unsigned)nfr);
   const int tile = rest % cp.ntile_c, pp = rest / cp.ntile_c;             // column tile, PSF plane
-  const long pl = (long)fr * g.DC + pp;
+  const long pl = (long)fr * g.PM + pp;
   const int c0 = tile * T;
   static_assert(!SL || T == 8, "pair lines hold 8 columns of two rows");
   const int cb = SL ? 2 * c0 : c0;                  // first element of the tile's column chunk within a row (pair)
@@ -2266,7 +2271,7 @@ __global__ __launch_bounds__(NT) void k_spectrum_mul_to_hwc(PlaneGeom g, const r
     const int p = (kr % N1) * N2 + kr / N1;
     const long q = img * g.C + c;
     const long off = (long)p * g.cpitch + kc;
-    const real2 v = S[q * g.cplane + off], h = Hs[(q % g.DC) * g.cplane + off];
+    const real2 v = S[q * g.cplane + off], h = Hs[(q % g.PM) * g.cplane + off];
     out[img * n + e] = conjH ? cmul_conj(v, h) : cmul(v, h);
   }
 }

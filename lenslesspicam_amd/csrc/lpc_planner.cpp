@@ -406,6 +406,7 @@ int setup_shape(const lpc_config& c, const EngineOpts& o, int cu, ShapePlan* out
   g.uplane = (long)g.H * g.W;
   g.DC = c.depth * c.channels;
   g.C = c.channels;
+  g.PM = g.DC;
   g.rev = 0;
   out->Ppsf = g.DC;
   out->P = c.batch * g.DC;

@@ -258,6 +258,7 @@ int alloc_common(Engine* e) {
   const PlaneGeom& g = e->g;
   LPC_OK(dev_alloc(e, &e->Hs, (size_t)g.cplane * e->Ppsf));
   LPC_OK(dev_alloc(e, &e->psf_planar, (size_t)g.uplane * e->Ppsf));
+  e->psf_cap = e->Ppsf;
   const int nspec = e->cfg.algo == LPC_ALGO_ADMM ? 2 : 1;
   LPC_OK(dev_alloc(e, &e->S, (size_t)g.cplane * e->P * nspec));
   if (e->cfg.algo != LPC_ALGO_CONV) return dev_alloc(e, &e->Y, (size_t)g.uplane * e->Pdata);
@@ -266,10 +267,44 @@ int alloc_common(Engine* e) {
   return dev_alloc(e, &e->conv_out, n);
 }
 
-int set_psf(Engine* e, const real* dev_psf) {
+// The handle holds n PSF planes from here on and addresses H by state plane q % n (PlaneGeom::PM): D*C planes, one PSF
+// for the batch, or batch*D*C, one per frame.  More planes than there is room for: Hs, psf_planar and ADMM's copies are
+// given back and allocated again for n planes (once per handle: they do not shrink)
+static int psf_planes(Engine* e, int n) {
   const PlaneGeom& g = e->g;
-  // (D,H,W,C) -> planar [D*C][H][W]
-  LPC_OK(hwc_to_planar(e, dev_psf, e->psf_planar, e->cfg.depth, g.H, g.W, g.W, g.uplane));
+  if (n > e->psf_cap) {
+    e->psf_set = false;
+    dev_free(e, e->Hs); dev_free(e, e->psf_planar);
+    e->Hs = nullptr; e->psf_planar = nullptr;
+    e->psf_cap = 0;
+    LPC_OK(dev_alloc(e, &e->Hs, (size_t)g.cplane * n));
+    LPC_OK(dev_alloc(e, &e->psf_planar, (size_t)g.uplane * n));
+    if (e->cfg.algo == LPC_ALGO_ADMM) LPC_OK(admm_alloc_psf(e, n));
+    e->psf_cap = n;
+  }
+  e->Ppsf = n;
+  e->g.PM = n;
+  return 0;
+}
+
+// nimg PSFs (D,H,W,C) each -> planar [nimg*D*C][H][W] -> their spectra, norm applied (+ the pair-line copy): one launch
+// sequence for all of them
+static int psf_spectra(Engine* e, const real* dev_psf, int npsf);
+
+int set_psf(Engine* e, const real* dev_psf) {
+  LPC_OK(psf_planes(e, e->g.DC));
+  e->psf_per_frame = false;
+  return psf_spectra(e, dev_psf, 1);
+}
+int set_psf_batch(Engine* e, const real* dev_psfs) {
+  LPC_OK(psf_planes(e, e->P));
+  e->psf_per_frame = true;
+  return psf_spectra(e, dev_psfs, e->cfg.batch);
+}
+
+static int psf_spectra(Engine* e, const real* dev_psf, int npsf) {
+  const PlaneGeom& g = e->g;
+  LPC_OK(hwc_to_planar(e, dev_psf, e->psf_planar, npsf * e->cfg.depth, g.H, g.W, g.W, g.uplane));
   LPC_OK(fft2_forward_setup(e, src_unpadded(e, e->psf_planar), e->Hs, e->Ppsf));
   double sc = 1.0;  // rfft_convolve.py:121 norm= of the PSF spectrum
   if (e->cfg.norm == LPC_NORM_ORTHO) sc = 1.0 / std::sqrt((double)g.Hp * (double)g.Wp);

@@ -101,6 +101,9 @@ class ReconstructionAlgorithm(_Boundary, abc.ABC):
         self._data_dev = None
         self._initial_est = None
         self._denoiser = None
+        self._psfs = None                # one PSF per measurement (_set_psfs); None: self._psf for all of them
+        self._psfs_dev = None
+        self._psfs_on = None             # the handle that holds them
         # geometry (rfft_convolve.py:110-117) -- queried from a throw-away operator config
         h = self._new_handle(batch=1)
         self._padded_shape = [int(psf.shape[0]), h.Hp, h.Wp, int(psf.shape[3])]
@@ -173,6 +176,7 @@ class ReconstructionAlgorithm(_Boundary, abc.ABC):
         B = int(d.shape[0])
         self._ensure_handle(B)
         self._data_dev = d[:, 0].contiguous()
+        self._sync_psfs(B)
         self._handle.set_data(self._data_dev.data_ptr(), int(d.shape[-1]), self._stream())
 
     def _check_est(self, image_est):
@@ -242,7 +246,40 @@ class ReconstructionAlgorithm(_Boundary, abc.ABC):
         assert isinstance(psf, type(self._psf)), "new PSF must have same type as old PSF"
         self._psf = psf
         self._psf_dev = self._to_dev(psf)
+        self._psfs = self._psfs_dev = self._psfs_on = None               # back to one PSF for every measurement
         self._handle.set_psf(self._psf_dev.data_ptr(), self._stream())  # implies reset()
+
+    # -- one PSF per measurement (additive: trainable_recon.py:346-350 takes a 5-D ``psfs`` in forward()) ---------------
+    _PER_FRAME_PSFS = False          # the solvers whose step and start value do not follow the PSF say True
+
+    def _set_psfs(self, psfs):
+        """``psfs``: (B, D, H, W, C), PSF b for measurement b of every later batch of B measurements, until the next
+        ``_set_psf``.  Inference only; ``self._psf`` stays what it was (the geometry, and what a gradient is taken of)."""
+        if not self._PER_FRAME_PSFS:
+            raise NotImplementedError(f"{type(self).__name__}: per-frame PSFs are not implemented (the step and the start "
+                                      "value of the plain gradient-descent solvers follow ONE PSF)")
+        assert isinstance(psfs, type(self._psf)), "new PSFs must have same type as old PSF"
+        assert len(psfs.shape) == 5 and tuple(psfs.shape[1:]) == tuple(self._psf.shape), \
+            f"per-frame PSFs must be of shape (B,) + {tuple(self._psf.shape)}"
+        self._psfs = psfs
+        self._psfs_dev = self._to_dev(psfs)
+        self._psfs_on = None
+        if self._handle_batch == int(psfs.shape[0]):
+            self._sync_psfs(self._handle_batch)
+
+    def _before_psfs(self):
+        """what the handle must know before it takes per-frame PSFs (unrolled FISTA: its schedule)"""
+
+    def _sync_psfs(self, batch):
+        """hands the per-frame PSFs to the handle of ``batch`` measurements unless it holds them already"""
+        if self._psfs_dev is None or self._psfs_on is self._handle:
+            return
+        if int(self._psfs_dev.shape[0]) != int(batch):
+            raise ValueError(f"{int(batch)} measurements against {int(self._psfs_dev.shape[0])} per-frame PSFs: the batch "
+                             "sizes must match (_set_psf returns to one PSF)")
+        self._before_psfs()
+        self._handle.set_psf_batch(self._psfs_dev.data_ptr(), self._stream())      # implies reset()
+        self._psfs_on = self._handle
 
     def _progress(self):
         return
@@ -261,11 +298,17 @@ class ReconstructionAlgorithm(_Boundary, abc.ABC):
         assert self._data.shape[0] == 1, "Apply doesn't supports processing multiple images at once."
         return self._apply_impl(n_iter, disp_iter, plot_pause, plot, save, gamma, ax, reset, background)[0]
 
-    def apply_batch(self, n_iter=None, reset=True, background=None, out=None):
+    def apply_batch(self, n_iter=None, reset=True, background=None, out=None, psfs=None):
         """Additive entry: B measurements sharing the PSF in one launch sequence.  Equals B
         independent ``apply()`` calls (frames never couple); returns (B,D,H,W,C).  ``out``: a device tensor the result is
-        written into (torch solvers on the engine's device only)."""
+        written into (torch solvers on the engine's device only).  ``psfs``: (B,D,H,W,C), one PSF per measurement
+        (ADMM; stays current for later batches of B measurements until ``_set_psf``): equals B times
+        ``_set_psf(psfs[b])``, ``set_data(data[b])``, ``apply()``."""
         assert self._data is not None, "Must set data with `set_data()`"
+        if psfs is not None:
+            assert len(psfs.shape) == 5 and int(psfs.shape[0]) == int(self._data.shape[0]), \
+                "psfs must hold one PSF per measurement: (B, D, H, W, C)"
+            self._set_psfs(psfs)
         return self._apply_impl(n_iter, None, 0.0, False, False, None, None, reset, background, out=out)[1]
 
     def _apply_impl(self, n_iter, disp_iter, plot_pause, plot, save, gamma, ax, reset, background, out=None):
@@ -316,7 +359,8 @@ class ReconstructionAlgorithm(_Boundary, abc.ABC):
     def reconstruction_error(self, prediction=None, lensless=None, psfs=None, normalize=True):
         """``|| norm(H x) - y ||^2 / npix`` per batch item (recon.py:607-653).  One convolution and
         three device reductions through ``lpc_reconstruction_error``; nothing is copied to the host
-        except the final value(s) when the solver was built from NumPy arrays."""
+        except the final value(s) when the solver was built from NumPy arrays.  A solver that holds per-frame PSFs
+        (``_set_psfs``) evaluates every item against its own; ``psfs`` may be 5-D, one PSF per prediction."""
         if prediction is None:
             prediction = self.get_image_estimate()
         if lensless is None:
@@ -339,11 +383,15 @@ class ReconstructionAlgorithm(_Boundary, abc.ABC):
             h = self._handle
         else:     # another PSF of the same shape (recon.py:631-633) or another batch size: a throw-away
             psf_dev = self._psf_dev if psfs is None else self._to_dev(psfs)      # operator handle
-            assert tuple(psf_dev.shape) == tuple(self._psf_dev.shape)
-            D, H, W, C = (int(v) for v in psf_dev.shape)
+            assert tuple(psf_dev.shape[-4:]) == tuple(self._psf_dev.shape)
+            D, H, W, C = (int(v) for v in psf_dev.shape[-4:])
             h = self._lib.create(algo=_native.ALGO_CONV, height=H, width=W, channels=C, depth=D, batch=B,
                                  norm=_native.NORM[self._norm], pad=1)
-            h.set_psf(psf_dev.data_ptr(), self._stream())
+            if psf_dev.dim() == 5:      # one PSF per batch item
+                assert int(psf_dev.shape[0]) == B, "psfs must hold one PSF per prediction: (B, D, H, W, C)"
+                h.set_psf_batch(psf_dev.data_ptr(), self._stream())
+            else:
+                h.set_psf(psf_dev.data_ptr(), self._stream())
         out = self._empty((B,))
         h.reconstruction_error(pred.data_ptr(), y.data_ptr(), bool(normalize), out.data_ptr(), self._stream())
         if not own:

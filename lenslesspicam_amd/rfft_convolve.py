@@ -6,6 +6,10 @@ convolve / deconvolve = hand-written real 2-D FFT (two real rows per complex LDS
 four-step column passes) with the multiplication by the PSF spectrum fused between the
 forward and inverse column passes; padding is done on load, ``ifftshift`` and cropping on
 store, so neither costs a pass over HBM.
+
+A 5-D PSF ``(B, D, H, W, C)`` is one PSF per batch item (rfft_convolve.py:55-58, 84-117): ``convolve`` / ``deconvolve`` /
+``return_fft=True`` then take ``(B, D|1, H, W, C|1)`` inputs, item b against PSF b, in one launch sequence
+(``lpc_set_psf_batch``).  ``_padded_shape`` stays ``[D, Hp, Wp, C]`` and ``_pad`` prepends the batch, as in the reference.
 """
 from __future__ import annotations
 
@@ -20,8 +24,8 @@ class RealFFTConvolve2D(_Boundary):
     def __init__(self, psf, dtype=None, pad=True, norm="ortho", rgb=None, **kwargs):
         self._init_boundary(psf, _check_dtype(dtype, isinstance(psf, torch.Tensor)))
         assert len(psf.shape) >= 4, "Expected 4D PSF of shape ([batch], depth, width, height, channels)"
-        if len(psf.shape) != 4:
-            raise NotImplementedError("batched PSFs (5-D) are used only by trainable models (out of scope)")
+        if len(psf.shape) > 5:
+            raise ValueError("Expected 4D PSF of shape ([batch], depth, width, height, channels)")
         self._use_3d = psf.shape[-4] != 1
         self._is_rgb = (psf.shape[-1] == 3) if rgb is None else rgb
         assert self._is_rgb or psf.shape[-1] == 1
@@ -52,20 +56,24 @@ class RealFFTConvolve2D(_Boundary):
         return vpad
 
     def _make(self, batch):
-        D, H, W, C = (int(s) for s in self._psf_dev.shape)
+        D, H, W, C = (int(s) for s in self._psf_dev.shape[-4:])
         if self._handle is not None:
             self._handle.close()
         self._handle = self._lib.create(algo=_native.ALGO_CONV, height=H, width=W, channels=C, depth=D,
                                         batch=int(batch), norm=_native.NORM[self.norm], pad=int(bool(self.pad)),
                                         options=self._engine_options)
         self._handle_batch = int(batch)
-        self._handle.set_psf(self._psf_dev.data_ptr(), self._stream())
+        if self._per_frame:      # (batch == the PSFs' own)
+            self._handle.set_psf_batch(self._psf_dev.data_ptr(), self._stream())
+        else:
+            self._handle.set_psf(self._psf_dev.data_ptr(), self._stream())
 
     def set_psf(self, psf):
         self._psf = psf.type(self.dtype) if isinstance(psf, torch.Tensor) else psf.astype(self.dtype)
         self._psf_dev = self._to_dev(psf)
         self._psf_shape = np.array(self._psf.shape)
-        self._make(max(self._handle_batch, 1))
+        self._per_frame = len(self._psf_shape) == 5          # one PSF per batch item
+        self._make(int(self._psf_shape[0]) if self._per_frame else max(self._handle_batch, 1))
         h = self._handle
         self._padded_shape = [int(self._psf_shape[-4]), h.Hp, h.Wp, 3 if self._is_rgb else 1]
         self._start_idx = np.array([h.sh, h.sw])
@@ -77,7 +85,10 @@ class RealFFTConvolve2D(_Boundary):
             raise ValueError("Expected 4D or 5D tensor")                     # rfft_convolve.py:91
         xd = self._to_dev(x)
         lead = xd.shape[:-4]
-        D, C = int(self._psf_shape[0]), int(self._psf_shape[-1])
+        D, C = int(self._psf_shape[-4]), int(self._psf_shape[-1])
+        if self._per_frame and (len(xd.shape) != 5 or int(xd.shape[0]) != int(self._psf_shape[0])):
+            raise ValueError(f"input of shape {tuple(xd.shape)} against {int(self._psf_shape[0])} per-frame PSFs: expected a "
+                             "5D tensor with the PSFs' batch size")
         want = tuple(int(v) for v in (self._psf_shape[-3:-1] if self.pad else self._padded_shape[-3:-1]))
         if tuple(int(v) for v in xd.shape[-3:-1]) != want:
             raise ValueError(f"input of spatial size {tuple(xd.shape[-3:-1])}, the operator works on {want}")
@@ -92,7 +103,7 @@ class RealFFTConvolve2D(_Boundary):
             # while the un-padded operator's `rfft2(x) * H` does: every channel is convolved with the one PSF
             # (only the reference's torch branch broadcasts; its NumPy branch writes into a (..., 1) scratch buffer,
             # `self._padded_data[:] = x`, rfft_convolve.py:143,171, which raises for three channels)
-            if self.pad or C != 1 or not self.is_torch:
+            if self.pad or C != 1 or not self.is_torch or self._per_frame:
                 raise ValueError(f"could not broadcast an input with {Cx} channels against a PSF with {C}")
             x5 = x5.permute(0, 4, 1, 2, 3).reshape((-1,) + tuple(x5.shape[1:4]) + (1,))    # channels -> batch items
             split3 = True

@@ -27,6 +27,13 @@ gradient, so that their forward under autograd stays what it was -- it keeps no 
 built with ``psf_grad=True`` (``psfs=`` or a PSF requiring a gradient), per-frame PSFs (a 5-D ``psfs``), the initial
 estimate, a custom ``psi`` and a denoiser.
 
+Inference takes one PSF per measurement: ``forward(batch, psfs=P5)`` with ``P5.shape == (B,) + psf.shape`` under
+``torch.no_grad()`` (or with nothing requiring a gradient) returns what B single-frame forwards with ``psfs=P5[b]`` return,
+in one launch sequence (``lpc_set_psf_batch``: the handle holds ``B D C`` PSF spectra).  ``P5`` stays current for later
+batches of B measurements, like the convolver the reference rebuilds and keeps (``trainable_recon.py:346-350``), until a
+4-D ``psfs=`` or ``_set_psf``; a forward that records refuses it.  ``background=`` and ``dist.*`` sharding of ``psfs`` are
+not supported.
+
 ``UnrolledADMM(psf, ..., psf_grad=True)`` makes the PSF an autograd input as well: ``forward(batch, psfs=p)`` with
 ``p.requires_grad``, or a ``p`` set earlier through ``_set_psf(p)``, gets ``dL/dp`` in ``p``'s shape, dtype and device,
 summed over the batch, from the same reverse sweep (``lpc_admm_backward_psf``: three cross terms per iteration -- through
@@ -196,10 +203,12 @@ class UnrolledADMM(_Taped, ADMM, torch.nn.Module):
         init_grad = isinstance(self._initial_est, torch.Tensor) and self._initial_est.requires_grad
         train = torch.is_grad_enabled() and (psf_grad or init_grad or any(t.requires_grad for t in [batch] + params))
         if train:
+            if self._per_frame(psfs):      # (a 4-D psfs below returns to one PSF: only the PSFs of THIS forward count)
+                self._refuse_per_frame_training(psfs)
             self._refuse_gradients(batch, psfs if psf_grad else None)
-        if psfs is not None:
-            self._set_psf(psfs)
+        self._take_psfs(batch, psfs)
         if train:
+            self._refuse_per_frame_training(None)
             psf = self._psf if self.psf_grad and isinstance(self._psf, torch.Tensor) and self._psf.requires_grad else None
             return _UnrolledADMMFunction.apply(self, batch, *params, psf).as_subclass(_Estimate)
         return self._run(batch)

@@ -22,7 +22,13 @@ its detached device copy).  As in the reference's ``forward(batch, psfs=...)``, 
 else (``trainable_recon.py:337-350``), the default start value and the steps derived from the constructor's PSF are
 constants.  The gradient costs a workspace of three spectra and one state array on top of the tape (include/lpc.h:
 ``lpc_fista_backward_psf``), allocated by the first backward that needs it and given back by ``release_tape()``.  One PSF
-for the batch: per-frame PSFs (a 5-D ``psfs``) raise ``NotImplementedError``.
+for the batch: per-frame PSFs (a 5-D ``psfs``) raise ``NotImplementedError`` from a forward that records.
+
+Inference takes one PSF per measurement: ``forward(batch, psfs=P5)`` with ``P5.shape == (B,) + psf.shape`` under
+``torch.no_grad()`` (or with nothing requiring a gradient) returns what B single-frame forwards with ``psfs=P5[b]`` return,
+in one launch sequence (``lpc_set_psf_batch``).  ``P5`` stays current for later batches of B measurements until a 4-D
+``psfs=`` or ``_set_psf``; the start value and ``_alpha_p`` stay the constructor's, as in the reference.  ``background=``
+and ``dist.*`` sharding of ``psfs`` are not supported.
 
 Pre- / post-processor networks are not taken by the constructor: the measurement and the PSF get gradients, so compose
 them in torch around ``forward()`` -- ``post(rec(pre(batch), psfs=psf + net(psf)))`` trains all of it.
@@ -90,6 +96,10 @@ class _UnrolledFISTAFunction(torch.autograd.Function):
 
 class UnrolledFISTA(_Taped, FISTA, torch.nn.Module):
     _record_method, _solver = "fista_record", "UnrolledFISTA"
+    _PER_FRAME_PSFS = True      # the schedule and the pinned start value replace what plain FISTA derives from its one PSF
+
+    def _before_psfs(self):
+        self._push_schedule()       # (lpc_set_psf_batch refuses a gradient-descent handle without one)
 
     def __init__(self, psf, n_iter=5, dtype=None, proj=non_neg, learn_tk=True, tk=1, skip_unrolled=False, **kwargs):
         assert isinstance(psf, torch.Tensor), "UnrolledFISTA takes torch tensors, like the reference"
@@ -175,12 +185,16 @@ class UnrolledFISTA(_Taped, FISTA, torch.nn.Module):
     def forward(self, batch, psfs=None, background=None):
         """``batch``: (B, D, H, W, C) -> (B, D, H, W, C) after exactly ``n_iter`` unrolled iterations."""
         self._check_forward_args(batch, psfs, background)
-        if psfs is not None:
-            self._set_psf(psfs)
         init = self._initial_est if isinstance(self._initial_est, torch.Tensor) else None
+        new_psf = psfs if isinstance(psfs, torch.Tensor) and psfs.dim() == 4 else self._psf
+        train = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                                for t in (batch, self._alpha_p, self._tk_p, init, new_psf, psfs))
+        if train and self._per_frame(psfs):
+            self._refuse_per_frame_training(psfs)
+        self._take_psfs(batch, psfs)
         psf = self._psf if isinstance(self._psf, torch.Tensor) and self._psf.requires_grad else None
-        if torch.is_grad_enabled() and any(t is not None and t.requires_grad
-                                           for t in (batch, self._alpha_p, self._tk_p, init, psf)):
+        if train:
+            self._refuse_per_frame_training(None)
             if self._hook:
                 raise NotImplementedError("UnrolledFISTA: only proj=non_neg is differentiated")
             if init is not None and not init.requires_grad:
