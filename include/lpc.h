@@ -94,7 +94,7 @@ typedef struct lpc_config {
  *   mid_swz=0|1        side-by-side middle: adjacent half-line column tiles on one XCD (default: when a tile row is < 128
  *                      bytes and the spectra are not in pair lines)
  *   spec_lay=0         ADMM work spectra as plain rows (default: paired rows + a single-pass middle of 8-column tiles keep
- *                      them in PAIR LINES -- rows 2p, 2p + 1 x 8 columns share one 128-byte line, lpc_kernels.h: spec_col)
+ *                      them in PAIR LINES -- rows 2p, 2p + 1 x 8 columns share one 128-byte line, lpc_args.h: spec_col)
  *   row_rad=16.16.8    radices of the compile-time row plan instead of the chooser's (one module)
  * The structure of an ADMM iteration (each setting is an older, complete form of the same arithmetic)
  *   xi_full=1 hv_full=1   without the sensor-window structure of xi / of the H V row transforms

@@ -2,6 +2,8 @@
 // custom-psi iterations around a caller's step, read-out of the state, and the byte models.  Every image-domain ADMM
 // kernel is launched from here; the row and column passes from lpc_rows.cpp / lpc_cols.cpp.
 #include "lpc_engine.h"
+#include "lpc_admm_kernels.h"
+#include "lpc_layout_kernels.h"
 #include "lpc_reduce_kernels.h"
 
 // ------------------------------------------------------------------------------ ADMM --

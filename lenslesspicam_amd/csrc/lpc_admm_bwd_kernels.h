@@ -29,7 +29,7 @@
 // AdmmBwdScalars.  The four sums leave every workgroup as double partial sums; k_admm_bwd_finish adds them in a fixed
 // order.  No atomics.
 #pragma once
-#include "lpc_kernels.h"
+#include "lpc_admm_kernels.h"
 
 struct AdmmBwdScalars {
   real m1, m2, m3, thr;      // iteration i

@@ -23,6 +23,7 @@
 // (window offset and frame width even); the planner checks (LaunchPlan::admm_rows_v2).
 #pragma once
 #include "lpc_gd_v2_kernels.h"
+#include "lpc_admm_kernels.h"
 
 #ifndef LPC_DOUBLE
 

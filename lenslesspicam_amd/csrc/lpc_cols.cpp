@@ -1,5 +1,5 @@
 // lpc_cols.cpp -- launches of every column pass (see lpc_engine.h for the split of the library)
-#include "lpc_engine.h"
+#include "lpc_launch.h"
 
 // column pass A (only when split) over nplanes planes; inverse => conj twiddles before FFT
 int cols_passA(Engine* e, real2* S, int nplanes, bool inverse, int zr0, int zr1, int kid,

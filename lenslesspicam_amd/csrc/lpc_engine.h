@@ -1,6 +1,6 @@
 // lpc_engine.h -- what the translation units of the engine share: the handle, error plumbing, the launcher and the
-// workgroup-shape dispatchers, the host functions that cross translation units, and the launches of the kernels that
-// the library and its plan modules both hold (lpc_launch.h; the gradient-descent family's: lpc_gd_launch.h).
+// workgroup-shape dispatchers, and the host functions that cross translation units.  It defines no kernel and includes
+// no header that does: a unit sees the kernels of the family headers it includes, and only those.
 //
 // One unit per role; the device compiler works on them in parallel, and a kernel is launched from the unit that
 // instantiates it:
@@ -22,8 +22,24 @@
 //   lpc_admm_bwd.cpp reverse mode of unrolled ADMM: its tape's layout, the replay and the sweep of lpc_admm_backward
 //   lpc_jit.cpp      plan modules: find / compile / load (lpc_plan.h)
 //   lpc_module.cpp   NOT part of the library: the source of a plan module (compile-time-plan kernels of one frame shape)
+//
+// One header per kernel family, each included by the units that launch from it (tests/test_kernel_headers.py: every
+// header compiles on its own, and lpc_abi.cpp, lpc_planner.cpp and lpc_jit.cpp see no kernel at all):
+//   lpc_args.h             frame geometry and the kernels' argument structs; no kernel           this header, every family
+//   lpc_row_kernels.h      row passes                                lpc_launch.h, lpc_gd_kernels.h, lpc_gd_bwd_kernels.h
+//   lpc_col_kernels.h      column passes and fused middles           lpc_launch.h
+//   lpc_admm_kernels.h     ADMM pixel arithmetic, image-domain kernels   lpc_admm.cpp, lpc_admm_bwd_kernels.h, the two below
+//   lpc_admm_row_kernels.h forward rows with ADMM work fused in (k_rfwd_half_x, k_rfwd_arrays_x)   lpc_module.cpp alone
+//   lpc_admm_v2_kernels.h  ... and the half-length ADMM rows in their second form                  lpc_module.cpp alone
+//   lpc_layout_kernels.h   layout / set-up kernels                   lpc_setup.cpp, lpc_admm.cpp
+//   lpc_reduce_kernels.h   workgroup reductions, min / max, gram separability   lpc_setup.cpp, lpc_admm.cpp, metric / prep
+//   lpc_gd_kernels.h, lpc_gd_v2_kernels.h   gradient-descent family's fused rows   lpc_gd_launch.h, lpc_gd_host.cpp, lpc_gd_update_p*.cpp
+//   lpc_gd_bwd_kernels.h, lpc_admm_bwd_kernels.h   the reverse modes    lpc_gd_bwd_launch.h, lpc_admm_bwd.cpp
+//   lpc_metric_kernels.h, lpc_prep_kernels.h   evaluation and raw-frame paths   lpc_eval.cpp
+// The launches of the kernels that the library and its plan modules both hold are written once, over the plan type:
+// lpc_launch.h (rows, columns), lpc_gd_launch.h, lpc_gd_bwd_launch.h; each includes this header and its kernels.
 #pragma once
-#include "lpc_kernels.h"
+#include "lpc_args.h"
 #include "lpc.h"
 #include "lpc_plan.h"
 
@@ -141,7 +157,7 @@ struct AdmmState {
   // copies of the PSF spectrum and |G| in the pair-line layout for the module's 8-column middle (PlaneGeom::slay)
   real2* Hs_t = nullptr;
   real* Gabs_t = nullptr;
-  // ... and the sequential middle's point-wise constants, precombined per (PSF, step sizes) (lpc_kernels.h: k_mid_consts)
+  // ... and the sequential middle's point-wise constants, precombined per (PSF, step sizes) (lpc_col_kernels.h: k_mid_consts)
   void* midc = nullptr;       // MidConst (mid_pc 1) or real2 (mid_pc 2: real phases) per element
   real* midrd = nullptr;
   double midc_par[3] = {0, 0, 0};   // the step sizes the tables were made for
@@ -499,5 +515,3 @@ int gd_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_alp
 int gd_bwd_rows(Engine* e, int mode, const GdBwd& a, const real2* Sin = nullptr);   // reverse-mode rows: 0 head, 1 middle, 2 update + next head, 3 PSF-gradient accumulate (rows of Sin)
 int gd_bwd_psf_sum(Engine* e, const real* acc, real* grad_psf); // ... and its sum over the batch -> (1, H, W, C)
 int gd_bwd_gdata(Engine* e, const real* gb, real* grad_data);   // planar data gradient -> the measurement's layout (both sweeps)
-
-#include "lpc_launch.h"

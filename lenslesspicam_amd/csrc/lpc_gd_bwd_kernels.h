@@ -21,7 +21,7 @@
 // The sums are deterministic: every workgroup (one image row, or one row pair) leaves its two partial sums, accumulated in
 // double, in a scratch array; k_gd_bwd_finish adds them up in a fixed order.  No atomics.
 #pragma once
-#include "lpc_kernels.h"
+#include "lpc_row_kernels.h"
 
 struct GdBwd {
   const real* alpha;   // [C] a_i of the iteration whose rows pass through (MODE 1, 2)

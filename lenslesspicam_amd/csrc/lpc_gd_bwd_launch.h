@@ -1,7 +1,7 @@
 // lpc_gd_bwd_launch.h -- lpc_gd_launch.h for the reverse-mode row kernels of unrolled FISTA (lpc_gd_bwd_kernels.h): the
 // half-row launches, written once for the core's run-time plans and the plan modules' compile-time plans.
 #pragma once
-#include "lpc_engine.h"
+#include "lpc_launch.h"
 #include "lpc_gd_bwd_kernels.h"
 
 // MODE 0: head of the last iteration -> rows (e->S);  1: rows (e->S) -> Hg, g_b -> rows (e->gd.S2);

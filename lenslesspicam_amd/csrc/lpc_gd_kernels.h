@@ -11,7 +11,7 @@
 //   [column passes, * conj(H) fused in the middle]
 //   k_rinv_gd_update   spectrum rows -> irfft -> shift+crop = grad -> fused update of x (+ momentum)
 #pragma once
-#include "lpc_kernels.h"
+#include "lpc_row_kernels.h"
 
 // ---- inverse rows -> residual -> forward rows, all inside the workgroup -------------------------
 // R2: plan_inv is the inverse-row plan with the radix-2 stage first (fused into the tangling, un-skewed

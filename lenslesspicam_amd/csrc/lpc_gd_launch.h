@@ -1,7 +1,7 @@
 // lpc_gd_launch.h -- lpc_launch.h for the gradient-descent family's fused row kernels.  Apart from it because
 // lpc_gd_kernels.h also holds plain (non-template) kernels, which every unit that includes it compiles.
 #pragma once
-#include "lpc_engine.h"
+#include "lpc_launch.h"
 #include "lpc_gd_kernels.h"
 
 // one real row per half-length transform (pa: the plan of length Wp / 2): H x rows (Sin) -> residual -> rows (Sout);

@@ -2,9 +2,13 @@
 // on a compile-time plan (SPlanArg, plan module): one function template per kernel family, over the workgroup shape, the
 // layout flags and the plan-argument type PA.  It alone names the kernel, builds its grid, sizes its LDS and lists its
 // arguments; the core calls it from dispatch_row / dispatch_cfg, lpc_module.cpp with its constants.  A template is
-// instantiated where it is called, so each kernel is still compiled in the unit that launches it.  (Included at the end
-// of lpc_engine.h; the gradient-descent family's fused rows: lpc_gd_launch.h.)
+// instantiated where it is called, so each kernel is still compiled in the unit that launches it.  (Included by
+// lpc_rows.cpp, lpc_cols.cpp, lpc_module.cpp and the gradient-descent family's launch headers, lpc_gd_launch.h and
+// lpc_gd_bwd_launch.h.)
 #pragma once
+#include "lpc_engine.h"
+#include "lpc_row_kernels.h"
+#include "lpc_col_kernels.h"
 
 static inline real2* spec_b(const Engine* e) { return e->S + (size_t)e->P * e->g.cplane; }   // second work spectrum (ADMM)
 static inline real inv_points(const PlaneGeom& g) { return (real)1.0 / ((real)g.Hp * (real)g.Wp); }   // unnormalised FFT pair

@@ -7,6 +7,7 @@
 // arrives as macros.
 #include "lpc_gd_launch.h"
 #include "lpc_gd_bwd_launch.h"
+#include "lpc_admm_row_kernels.h"
 #include "lpc_gd_v2_kernels.h"
 #include "lpc_admm_v2_kernels.h"
 

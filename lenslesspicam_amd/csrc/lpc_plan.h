@@ -52,7 +52,7 @@ struct PlanSpec {
   int mid_pre = 0;            // sequential middle: both tiles' loads issued before the first transform
   int mid_pc = 0;             // sequential middle on pair-line spectra: point-wise constants precombined (k_mid_consts): 1 two
                               // complex constants per element, 2 one (even padded sizes: the ifftshift phases are +-1)
-  int slay = 0;               // ADMM work spectra in pair lines (lpc_kernels.h: spec_col): paired rows + 8-column sequential middle
+  int slay = 0;               // ADMM work spectra in pair lines (lpc_args.h: spec_col): paired rows + 8-column sequential middle
   bool any() const { return row_kind != LPC_ROWS_RUNTIME || passA.n || mid_kind != LPC_MID_RUNTIME; }
 };
 

@@ -303,7 +303,7 @@ void choose_plan(const lpc_config& c, const EngineOpts& o, const PlaneGeom& g, i
       sp.mid = StaticFft{};
     }
   }
-  // pair-line work spectra (lpc_kernels.h: spec_col): paired rows + a single-pass middle of 8-column tiles, float32 (a tile row
+  // pair-line work spectra (lpc_args.h: spec_col): paired rows + a single-pass middle of 8-column tiles, float32 (a tile row
   // of 8 complex128 columns is a whole line already)
   sp.slay = (admm && f32 && sp.row_kind == LPC_ROWS_PAIRED && sp.mid_kind != LPC_MID_RUNTIME && pl.N1 == 1 && sp.mid.T == 8 &&
              o.spec_lay != 0) ? 1 : 0;

@@ -1,7 +1,7 @@
 // lpc_reduce_kernels.h -- workgroup reductions (wavefront shuffles, then lane 0 combines the waves) and the set-up
 // kernels built on them: per-plane min / max, and the separability check of ADMM's gram plane.
 #pragma once
-#include "lpc_kernels.h"
+#include "lpc_args.h"
 
 template <int NT>
 static __device__ __forceinline__ void block_minmax(real& mx, real& mn, real* scratch, int tid) {

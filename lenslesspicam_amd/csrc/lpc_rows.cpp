@@ -1,5 +1,5 @@
 // lpc_rows.cpp -- launches of every row pass (see lpc_engine.h for the split of the library)
-#include "lpc_engine.h"
+#include "lpc_launch.h"
 
 // ------------------------------------------------------------- 2-D transform pieces --
 // forward rows of ONE real source (pairs of rows) into spectrum S (planes = nplanes)

@@ -3,6 +3,7 @@
 // The layout, fill and plane min / max kernels are instantiated here alone; other units call the host functions
 // (declared in lpc_engine.h).
 #include "lpc_engine.h"
+#include "lpc_layout_kernels.h"
 #include <mutex>
 #include <unordered_map>
 #include "lpc_reduce_kernels.h"

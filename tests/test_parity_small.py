@@ -637,7 +637,7 @@ def test_c4_sequential_middle_frames_fastest_block_order(backend):
 
 
 def test_pair_line_spectra_odd_window_and_odd_height(backend):
-    """Pair-line work spectra (lpc_kernels.h: spec_col -- rows (2p, 2p + 1) x 8 columns of a half spectrum share one
+    """Pair-line work spectra (lpc_args.h: spec_col -- rows (2p, 2p + 1) x 8 columns of a half spectrum share one
     128-byte line; paired rows + a single-pass middle of 8-column tiles): the window's row pairs are aligned to even rows,
     so a window that starts on an ODD row (270 x 480: sh = 135; 23 x 40: sh = 11) gets a first and a last pair with one
     row that is neither formed nor stored, and an odd padded height (45) a last pair of one row.  Long enough calls to run

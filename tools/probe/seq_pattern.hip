@@ -1,5 +1,5 @@
 // seq_pattern.hip -- calibration of the memory-side counters on the access pattern of C4's sequential ADMM middle
-// (k_cols_mid_admm_seq, lenslesspicam_amd/csrc/lpc_kernels.h): VERDICT r04 item 2, MI355X_MICROARCH.md "HBM" -- the
+// (k_cols_mid_admm_seq, lenslesspicam_amd/csrc/lpc_col_kernels.h): VERDICT r04 item 2, MI355X_MICROARCH.md "HBM" -- the
 // 2 x FETCH_SIZE correction is calibrated for 16-byte-lane streaming only.
 //
 // A workgroup of 512 lanes owns ONE tile of T = 8 image columns x N = 540 rows of a half-spectrum plane (row pitch
