@@ -115,6 +115,10 @@ typedef struct lpc_config {
  *   admm_rows_v2=BITS  the second form of the half-length row kernels (lpc_admm_v2_kernels.h; wherever the row plan has one
  *                      radix and the window offset / width are even; float32; same bits as the first form): 1 the forward
  *                      rows with the X half (default), 2 the inverse rows (slower at 12 MP), 3 both; 0: first form
+ *   hv_fuse=0          H V written and read back between the iterations of one call (default 1: where bit 0 of admm_rows_v2,
+ *                      the H V row skipping and xi_half are on and the row plan is 16.16.16, every iteration but the last
+ *                      three of a call keeps the sensor window's rows of H V in registers -- inverse row, the next X half
+ *                      and forward row in one kernel, k_hv_rows_v2 -- same bits; 2: that launch behind the rows of V)
  * Block orders (permutations)
  *   rev_order=BITS     which ADMM kernels walk their grids backwards (1 tiled kernel, 2 / 4 forward / inverse pass A,
  *                      8 LDS middle; default 9);  gd_rev=BITS (gradient-descent family / operator: 1 residual rows, 2

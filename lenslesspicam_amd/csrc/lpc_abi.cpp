@@ -492,7 +492,8 @@ int lpc_plan_info(lpc_handle e, char* buf, size_t n) {
                                       : " (xi inside the sensor window only)";
     if (pl.rho_rsp || pl.xi_half)
       s += std::string("; inside a call: ") + (pl.rho_rsp ? "rho read back from r_sp" : "") +
-           (pl.rho_rsp && pl.xi_half ? ", " : "") + (pl.xi_half ? "xi half-applied" : "");
+           (pl.rho_rsp && pl.xi_half ? ", " : "") + (pl.xi_half ? "xi half-applied" : "") +
+           (pl.hv_fuse ? (pl.hv_fuse == 2 ? ", H V rows on chip (behind the rows of V)" : ", H V rows on chip") : "");
   }
   if (e->cfg.algo == LPC_ALGO_ADMM && e->admm.g_sep) s += "; gram as row + column terms";
   if (e->cfg.algo == LPC_ALGO_FISTA)      // lpc_fista_backward (lpc_gd_bwd.cpp: gd_bwd_rows)

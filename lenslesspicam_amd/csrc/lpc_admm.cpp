@@ -17,14 +17,16 @@ static void admm_params(const Engine* e, long it, double out[4]) {
   }
 }
 
-static AdmmScalars admm_scalars(const Engine* e, const double cur[4]) {
+// prev_par: the step sizes of the iteration before, for an iteration that is not the next to run (admm_iterate: the X half
+// that rides in the previous iteration's H V rows); else the engine's record
+static AdmmScalars admm_scalars(const Engine* e, const double cur[4], const double* prev_par = nullptr) {
   AdmmScalars p;
   p.mu1 = (real)cur[0]; p.mu2 = (real)cur[1]; p.mu3 = (real)cur[2];
   p.thr = (real)(cur[3] / cur[1]);               // admm.py:246: python-double division, then float32
   p.m_in = (real)1.0 / ((real)1.0 + p.mu1);                 // admm.py:193 in float32
   p.m_out = (real)1.0 / ((real)0.0 + p.mu1);
-  p.first = e->first ? 1 : 0;
-  const double* prev = e->first ? cur : e->admm.last_par;
+  p.first = (e->first && !prev_par) ? 1 : 0;
+  const double* prev = prev_par ? prev_par : e->first ? cur : e->admm.last_par;
   p.mu1p = (real)prev[0]; p.mu2p = (real)prev[1]; p.mu3p = (real)prev[2];
   p.thrp = (real)(prev[3] / prev[1]);
   p.m_in_p = (real)1.0 / ((real)1.0 + p.mu1p);
@@ -152,12 +154,23 @@ int admm_reset(Engine* e) {
 
 // (r_sp, a) in e->admm.Rsp / e->admm.Aarr  ->  Vout = irfft2(R_div (rfft2 r_sp + s H* rfft2 a)),  HVout = H Vout:
 // forward rows, [pass A], fused middle, [inverse pass A], inverse rows
+// a_done: the rows of `a` are in SB already, the forward rows run r_sp alone; next: the window's rows of H V stay on chip
+// (LaunchPlan::hv_fuse) -- k_hv_rows_v2 turns them into the rows of `a` of the iteration whose scalars *next holds, the
+// inverse rows write V alone and HVout is not touched
 static int admm_spectral_step(Engine* e, const AdmmScalars& sc, real* Vout, real* HVout, bool xhalf = false,
-                              const K1Rows* k1 = nullptr) {
-  if (xhalf) LPC_OK(e->mod->admm_rows_fwd_x(e, &sc, k1));   // (LaunchPlan::xhalf_rows: the module holds it)
+                              const K1Rows* k1 = nullptr, bool a_done = false, const AdmmScalars* next = nullptr) {
+  if (xhalf) LPC_OK(e->mod->admm_rows_fwd_x(e, &sc, k1, a_done ? 1 : 0));   // (LaunchPlan::xhalf_rows: the module holds it)
   else LPC_OK(admm_rows_fwd(e));
   LPC_OK(admm_cols(e, sc));
-  return admm_rows_inv(e, Vout, HVout, sc.skiphv != 0);
+  if (!next) return admm_rows_inv(e, Vout, HVout, sc.skiphv ? ADMM_HV_ROWS_WINDOW : ADMM_HV_ROWS_ALL);
+  // two launches, one entry of the per-iteration profile.  The fused rows first: inverse pass A ends on the planes of SB,
+  // and the tiled kernel that follows walks backwards from the tail of V (hv_fuse = 2: the other order, for measurements)
+  size_t slot = 0;
+  LPC_OK(timer_span_begin(e, LPC_K_ROW_INV, &slot));
+  if (e->plan.hv_fuse == 2) LPC_OK(admm_rows_inv(e, Vout, HVout, ADMM_HV_ROWS_NONE));
+  LPC_OK(e->mod->admm_rows_hv(e, next));
+  if (e->plan.hv_fuse != 2) LPC_OK(admm_rows_inv(e, Vout, HVout, ADMM_HV_ROWS_NONE));
+  return timer_span_end(e, LPC_K_ROW_INV, slot);
 }
 // ... with the step sizes `par` and nothing skipped: the spectral step of the reverse sweep (lpc_admm_bwd.cpp)
 int admm_spectral_plain(Engine* e, const double par[4], real* Vout, real* HVout) {
@@ -187,6 +200,7 @@ int admm_iterate(Engine* e, int n_iter) {
   const PlaneGeom& g = e->g;
   const LaunchPlan& pl = e->plan;
   bool sb_rows_valid = false;   // AdmmScalars::skipa may rely on the rows of SB only after a step of this very call
+  bool a_done = false;          // ... and the previous step of this call has left the window's rows of `a` there too (hv_fuse)
   for (int it = 0; it < n_iter; ++it) {
     real* Vc = e->admm.V[e->admm.vcur];
     real* Vo = e->admm.V[e->admm.vcur ^ 1];
@@ -226,7 +240,22 @@ int admm_iterate(Engine* e, int n_iter) {
     e->first = false;
     // (hcur still names the CURRENT H V here: the X half inside the forward rows reads HVb[hcur] and HVb[hcur ^ 1]
     // before the inverse rows of this same step overwrite HVb[hcur ^ 1] -- stream order)
-    LPC_OK(admm_spectral_step(e, sc, Vo, e->admm.HVb[e->admm.hcur ^ 1], pl.xhalf_rows, pl.k1 == ADMM_K1_ROWS ? &k1 : nullptr));
+    // H V on chip (LaunchPlan::hv_fuse): under the condition of skiphv -- the last three iterations of a call run complete --
+    // this step's H V rows do the X half of iteration it + 1 themselves, with that iteration's scalars (mu1 is its step size,
+    // mu1p this one's).  Iteration it + 1 is a steady-state one (xi half-applied on both sides, no xi_store, skipa): the form
+    // k_rfwd_half_x_v2 would run.  The H V buffers keep flipping but are STALE from here until the last three iterations
+    // rewrite them; nothing reads them in between: the tiled TV / W kernel does not, H V_old is not read with xi_in, the
+    // tape records V, and every read-out comes after the call.
+    const bool fuse = pl.hv_fuse && sc.skiphv && pl.xi_half && sc.xiw;
+    AdmmScalars scn{};
+    if (fuse) {
+      double parn[4];
+      admm_params(e, e->iters_done + 1, parn);
+      scn = admm_scalars(e, parn, par);
+    }
+    LPC_OK(admm_spectral_step(e, sc, Vo, e->admm.HVb[e->admm.hcur ^ 1], pl.xhalf_rows, pl.k1 == ADMM_K1_ROWS ? &k1 : nullptr,
+                              a_done, fuse ? &scn : nullptr));
+    a_done = fuse;
     e->admm.vcur ^= 1;  // Vo now holds the new image estimate
     e->admm.hcur ^= 1;  // ... and the other H V buffer its forward model
     sb_rows_valid = true;   // the inverse column passes of this step left rfft(H V row) / Wp in every row of SB
@@ -394,7 +423,8 @@ int admm_kernel_bytes(Engine* e, int kid, double* bytes) {
   const double R0 = eb * g.H * g.W * e->Pdata;
   const double Sc = 2 * eb * g.Hp * g.Wc * e->Ppsf;   // spectral constants
   const bool split = pl.N1 > 1, k1_rows = pl.k1 == ADMM_K1_ROWS;
-  const double fr = (double)g.H / (double)g.Hp;
+  // fr R, fr S with fr = H / Hp: the window's rows of a padded array / of a half spectrum (whole numbers, like every term here)
+  const double Rh = eb * g.H * g.Wp * e->P, Sh = 2 * eb * g.H * g.Wc * e->P;
   const double nxw = pl.xi_half ? 2.0 : 3.0;          // arrays the X half moves where xi lives: xi in, xi out (+ H V_old)
   double b = 0.0;
   switch (kid) {
@@ -414,14 +444,17 @@ int admm_kernel_bytes(Engine* e, int kid, double* bytes) {
     // ... and with the H V row transforms skipped on rows wholly outside the window (AdmmScalars::skipa, steady state
     // of a long call; fr = H / Hp): rows fwd (1 + fr) R + 3 Rw + R0 + (1 + fr) S, rows inv (1 + fr) (S + R)
     // ... and with xi half-applied between the iterations of a call (xi_half) H V_old is not read where xi is: 2 Rw
-    case LPC_K_ROW_FWD: b = (pl.hv_skip ? (1.0 + fr) * R + nxw * eb * g.H * g.W * e->P + R0 + (1.0 + fr) * S
+    // ... and with H V on chip (hv_fuse, the steady state of a call): rows fwd R + S (r_sp alone); rows inv = the rows of
+    // V, S + R, + the fused rows of the window, 2 fr S + 2 Rw + R0 -- the row of H V (2 fr R in all) does not move
+    case LPC_K_ROW_FWD: b = (pl.hv_fuse ? R + S : pl.hv_skip ? R + Rh + nxw * eb * g.H * g.W * e->P + R0 + S + Sh
                                 : pl.xi_window ? 2.0 * R + nxw * eb * g.H * g.W * e->P + R0 + 2.0 * S
                                 : pl.xhalf_rows ? (2.0 + nxw) * R + R0 + 2.0 * S : 2.0 * R + 2.0 * S)
                                + (k1_rows ? (pl.k1_half ? 6.0 : 7.0) * R : 0.0); break;
     case LPC_K_COL_A_FWD: b = split ? 4.0 * S : 0.0; break;
     case LPC_K_COL_MID: b = 4.0 * S + Sc + (e->admm.g_sep ? 0. : eb * g.Hp * g.Wc); break;  // + H (complex) + |G| (real, one plane; two vectors when it separates)
     case LPC_K_COL_A_INV: b = split ? 4.0 * S : 0.0; break;
-    case LPC_K_ROW_INV: b = pl.hv_skip ? (1.0 + fr) * (S + R) : 2.0 * S + 2.0 * R; break;
+    case LPC_K_ROW_INV: b = pl.hv_fuse ? S + R + 2.0 * Sh + 2.0 * eb * g.H * g.W * e->P + R0
+                               : pl.hv_skip ? S + Sh + R + Rh : 2.0 * S + 2.0 * R; break;
     default: return fail("bad kernel id");
   }
   *bytes = b;

@@ -106,6 +106,7 @@ struct KernelTimer {
 #endif
   bool on = false;
   unsigned mask = ~0u;      // bit k: launches of kernel id k are bracketed (lpc_profile_enable)
+  int span = -1;            // kernel id whose launches share ONE event pair at the moment (timer_span_begin): not bracketed singly
 };
 
 // ADMM image-domain kernel (K1): inside the forward rows (TV / W half and X half: three launches per iteration); tiled
@@ -113,6 +114,9 @@ struct KernelTimer {
 enum AdmmK1 { ADMM_K1_ROWS, ADMM_K1_TV_W, ADMM_K1_TILED, ADMM_K1_SCALAR };
 // ADMM fused middle: 24-point pass B in registers; the plan module's LDS middle; run-time plan in LDS on 512 threads x 18
 // points, or on the workgroup shape of its tile size
+// the rows of H V the inverse rows write: all; those of the sensor window (AdmmScalars::skiphv); none -- V alone, the window's
+// rows of SB go through admm_rows_hv instead (LaunchPlan::hv_fuse)
+enum AdmmHvRows { ADMM_HV_ROWS_ALL = 0, ADMM_HV_ROWS_WINDOW = 1, ADMM_HV_ROWS_NONE = 2 };
 enum AdmmMid { ADMM_MID_REG24, ADMM_MID_MODULE, ADMM_MID_RT_512X18, ADMM_MID_RT_LDS };
 
 // The launch plan of a handle: every kernel, tile shape, block order and fusion it runs, decided once at lpc_create
@@ -133,6 +137,9 @@ struct LaunchPlan {
   bool xi_half = false;    // ... xi half-applied too: the X half does not read H V_old where xi lives (AdmmScalars::xi_in)
   int admm_rows_v2 = 0;    // half-length rows in their second form (lpc_admm_v2_kernels.h; option admm_rows_v2): bit 0 the
                            // forward rows with the X half, bit 1 the inverse rows
+  int hv_fuse = 0;         // ... and between the steady-state iterations of a call H V stays on chip: inverse row, the next X half and
+                           // forward row of `a` in one kernel (k_hv_rows_v2; option hv_fuse).  1: that launch in front of the rows
+                           // of V, 2: behind them
   int k1_xcd_order = 0;    // K1Rows::xcd_order
   AdmmMid admm_mid = ADMM_MID_RT_LDS;
   int conv_mid_reg = 0;    // convolution middle (conv_middle) in registers: its pass-B length; 0: in LDS
@@ -331,24 +338,52 @@ static inline int tape_record(Engine* e, Tape& t, int on, int (*alloc)(Engine*))
 // thread_local set there would register a TLS destructor that pins the module: dlclose() would never unload it
 int big_smem_once(const void* fn, size_t smem);
 
+// event bracketing of hot-loop kernels: one pair per launch, or one pair around the launches of kernel id `kid` between
+// timer_span_begin and timer_span_end (two launches that are one entry of the per-iteration profile)
+#if !defined(LPC_SIMT_EMU)
+static inline bool timer_wants(const LaunchCtx* e, int kid) { return e->timer.on && kid >= 0 && ((e->timer.mask >> kid) & 1u); }
+static inline int timer_open(LaunchCtx* e, int kid, size_t* slot) {
+  auto& v = e->timer.ev[kid];
+  *slot = e->timer.used[kid]++;
+  if (*slot >= v.size()) {
+    hipEvent_t a, b;
+    LPC_RT(hipEventCreate(&a));
+    LPC_RT(hipEventCreate(&b));
+    v.push_back({a, b});
+  }
+  LPC_RT(hipEventRecord(v[*slot].first, e->stream));
+  return 0;
+}
+#endif
+static inline int timer_span_begin(LaunchCtx* e, int kid, size_t* slot) {
+#if !defined(LPC_SIMT_EMU)
+  if (!timer_wants(e, kid)) return 0;
+  LPC_OK(timer_open(e, kid, slot));
+  e->timer.span = kid;
+#else
+  (void)e; (void)kid; (void)slot;
+#endif
+  return 0;
+}
+static inline int timer_span_end(LaunchCtx* e, int kid, size_t slot) {
+#if !defined(LPC_SIMT_EMU)
+  if (e->timer.span != kid) return 0;
+  e->timer.span = -1;
+  LPC_RT(hipEventRecord(e->timer.ev[kid][slot].second, e->stream));
+#else
+  (void)e; (void)kid; (void)slot;
+#endif
+  return 0;
+}
+
 // generic launcher (+ optional event bracketing of hot-loop kernels)
 template <class K, class... A>
 static inline int launch_k(LaunchCtx* e, int kid, K kernel, dim3 grid, int nt, size_t smem, A... args) {
   if (smem > 48 * 1024) LPC_OK(big_smem_once((const void*)kernel, smem));
 #if !defined(LPC_SIMT_EMU)
-  const bool timed = e->timer.on && kid >= 0 && ((e->timer.mask >> kid) & 1u);
+  const bool timed = timer_wants(e, kid) && kid != e->timer.span;
   size_t slot = 0;
-  if (timed) {
-    auto& v = e->timer.ev[kid];
-    slot = e->timer.used[kid]++;
-    if (slot >= v.size()) {
-      hipEvent_t a, b;
-      LPC_RT(hipEventCreate(&a));
-      LPC_RT(hipEventCreate(&b));
-      v.push_back({a, b});
-    }
-    LPC_RT(hipEventRecord(v[slot].first, e->stream));
-  }
+  if (timed) LPC_OK(timer_open(e, kid, &slot));
   hipLaunchKernelGGL(kernel, grid, dim3(nt), smem, e->stream, args...);
   if (timed) LPC_RT(hipEventRecord(e->timer.ev[kid][slot].second, e->stream));
 #else
@@ -403,8 +438,11 @@ struct LpcModule {
   int (*rows_fwd_single)(Engine*, const RealSrc*, real2* S, int nplanes, int kid);
   int (*rows_inv_single)(Engine*, const real2* S, const RealDst*, int nplanes, int kid);
   int (*admm_rows_fwd)(Engine*);
-  int (*admm_rows_fwd_x)(Engine*, const AdmmScalars*, const K1Rows* k1);   // k1: + the TV / W half (k1_rows)
-  int (*admm_rows_inv)(Engine*, real* Vout, real* HVout, int skip_hv_outside);
+  // k1: + the TV / W half (k1_rows); a_done: the rows of `a` are in SB already (admm_rows_hv), r_sp alone
+  int (*admm_rows_fwd_x)(Engine*, const AdmmScalars*, const K1Rows* k1, int a_done);
+  int (*admm_rows_inv)(Engine*, real* Vout, real* HVout, int hv_rows);      // hv_rows: ADMM_HV_ROWS_*
+  // H V rows on chip (k_hv_rows_v2): the window's rows of SB -> H V -> X half with the NEXT iteration's scalars -> rows of `a`
+  int (*admm_rows_hv)(Engine*, const AdmmScalars* next);
   int (*gd_rows_mid)(Engine*, const real2* Sin, real2* Sout);
   int (*gd_rows_update)(Engine*, const GdScalars*, const real* alpha);
   int (*gd_rows_update_fwd)(Engine*, const GdScalars*, const real* alpha);
@@ -494,7 +532,7 @@ double gd_model_bytes(const Engine* e);
 int rows_fwd_single(Engine* e, const RealSrc& src, real2* S, int nplanes, int kid);
 int rows_inv_single(Engine* e, const real2* S, const RealDst& dst, int nplanes, int kid);
 int admm_rows_fwd(Engine* e);                                   // e->admm.Rsp, e->admm.Aarr -> the two work spectra
-int admm_rows_inv(Engine* e, real* Vout, real* HVout, bool skip_hv_outside = false);          // the two work spectra -> V, H V
+int admm_rows_inv(Engine* e, real* Vout, real* HVout, int hv_rows = ADMM_HV_ROWS_ALL);          // the two work spectra -> V, H V
 // lpc_cols.cpp
 int cols_passA(Engine* e, real2* S, int nplanes, bool inverse, int zr0, int zr1, int kid, bool crop_rows_only = false,
                real sb_outside_scale = (real)0.);

@@ -12,6 +12,10 @@
 
 static inline real2* spec_b(const Engine* e) { return e->S + (size_t)e->P * e->g.cplane; }   // second work spectrum (ADMM)
 static inline real inv_points(const PlaneGeom& g) { return (real)1.0 / ((real)g.Hp * (real)g.Wp); }   // unnormalised FFT pair
+// the half-length inverse rows' grid.x by the rows of H V they write (k_rinv_half: skip_b_outside)
+static inline unsigned admm_rows_inv_grid(const PlaneGeom& g, int hv_rows) {
+  return (unsigned)(hv_rows == ADMM_HV_ROWS_NONE ? g.Hp : hv_rows == ADMM_HV_ROWS_WINDOW ? g.Hp + g.H : 2 * g.Hp);
+}
 static inline PlaneGeom geom_rev(const Engine* e, bool rev) {   // the launch's copy of the geometry (PlaneGeom::rev)
   PlaneGeom g = e->g;
   g.rev = rev ? 1 : 0;
@@ -29,7 +33,7 @@ static inline int launch_rows_inv_half(Engine* e, const PA& pa, const real2* S, 
   return launch_k(e, kid, k_rinv_rows_half<NT, EM, SK, PA>, dim3(dst.nrows, nplanes), NT,
                   LPC_ROW_SMEM_BYTES(e->g.Wp / 2, SK), e->g, pa, e->planW.tw, S, dst);
 }
-// ADMM: e->admm.Rsp, e->admm.Aarr -> the two work spectra, and back to V, H V (skip_hv: H V on the rows of the sensor window alone)
+// ADMM: e->admm.Rsp, e->admm.Aarr -> the two work spectra, and back to V, H V (hv_rows: ADMM_HV_ROWS_*)
 template <int NT, int EM, int SK, class PA>
 static inline int launch_admm_rows_fwd_half(Engine* e, const PA& pa) {
   return launch_k(e, LPC_K_ROW_FWD, k_rfwd_half<NT, EM, SK, PA>, dim3(2 * e->g.Hp, e->P), NT,
@@ -37,11 +41,11 @@ static inline int launch_admm_rows_fwd_half(Engine* e, const PA& pa) {
                   e->S, spec_b(e));
 }
 template <int NT, int EM, int SK, class PA>
-static inline int launch_admm_rows_inv_half(Engine* e, const PA& pa, real* Vout, real* HVout, bool skip_hv) {
+static inline int launch_admm_rows_inv_half(Engine* e, const PA& pa, real* Vout, real* HVout, int hv_rows) {
   const PlaneGeom& g = e->g;
-  return launch_k(e, LPC_K_ROW_INV, k_rinv_half<NT, EM, SK, PA>, dim3(skip_hv ? g.Hp + g.H : 2 * g.Hp, e->P), NT,
+  return launch_k(e, LPC_K_ROW_INV, k_rinv_half<NT, EM, SK, PA>, dim3(admm_rows_inv_grid(g, hv_rows), e->P), NT,
                   LPC_ROW_SMEM_BYTES(g.Wp / 2, SK), g, pa, e->planW.tw, (const real2*)e->S, (const real2*)spec_b(e),
-                  Vout, HVout, skip_hv ? 1 : 0);
+                  Vout, HVout, hv_rows);
 }
 
 // ---- ADMM rows, two real rows per complex transform of length Wp (SL: PlanSpec::slay) ---------------------------

@@ -55,25 +55,43 @@ static int m_rows_inv_single(Engine* e, const real2* S, const RealDst* dst, int 
 static constexpr int V2SK = LPC_MOD_V2_SK;
 static const size_t kV2Smem = LPC_ROW_SMEM_BYTES(RowP::n, V2SK);
 static int m_admm_rows_fwd(Engine* e) { return launch_admm_rows_fwd_half<RNT, REM, RSK>(e, row_arg(e)); }
-static int m_admm_rows_inv(Engine* e, real* Vout, real* HVout, int skip_hv_outside) {
+static int m_admm_rows_inv(Engine* e, real* Vout, real* HVout, int hv_rows) {
 #ifndef LPC_DOUBLE
   if constexpr (GdV2<RowP>::ok) {
     if (e->plan.admm_rows_v2 & 2) {
       const PlaneGeom& g = e->g;
       constexpr int NB = GdV2<RowP>::NB;
-      return launch_k(e, LPC_K_ROW_INV, k_rinv_half_v2<NB, V2SK, RowPA>, dim3(skip_hv_outside ? g.Hp + g.H : 2 * g.Hp, e->P), NB,
+      return launch_k(e, LPC_K_ROW_INV, k_rinv_half_v2<NB, V2SK, RowPA>, dim3(admm_rows_inv_grid(g, hv_rows), e->P), NB,
                       kV2Smem, g, row_arg(e), (const real2*)e->planW.tw, (const real2*)e->S, (const real2*)spec_b(e), Vout,
-                      HVout, skip_hv_outside ? 1 : 0);
+                      HVout, hv_rows);
     }
   }
 #endif
-  return launch_admm_rows_inv_half<RNT, REM, RSK>(e, row_arg(e), Vout, HVout, skip_hv_outside != 0);
+  return launch_admm_rows_inv_half<RNT, REM, RSK>(e, row_arg(e), Vout, HVout, hv_rows);
 }
+#if LPC_MOD_ROW_X && !defined(LPC_DOUBLE)
+// LaunchPlan::hv_fuse: the window's rows of SB -> H V in registers -> X half of the next iteration (*next) -> rows of `a`, in place
+static int m_admm_rows_hv(Engine* e, const AdmmScalars* next) {
+  if constexpr (GdV2<RowP>::ok) {
+    constexpr int NB = GdV2<RowP>::NB;
+    return launch_k(e, LPC_K_ROW_INV, k_hv_rows_v2<NB, V2SK, RowPA>, dim3(e->g.H, e->P), NB, kV2Smem, e->g, *next, row_arg(e),
+                    (const real2*)e->planW.tw, spec_b(e), e->admm.xi, (const real*)e->Y, make_fastdiv((unsigned)e->g.DC),
+                    make_fastdiv((unsigned)e->g.C));
+  }
+  return fail("internal: this module's rows have no second form");
+}
+#endif
 #if LPC_MOD_ROW_X
-static int m_admm_rows_fwd_x(Engine* e, const AdmmScalars* sc, const K1Rows* k1) {
+static int m_admm_rows_fwd_x(Engine* e, const AdmmScalars* sc, const K1Rows* k1, int a_done) {
   if (k1) return fail("internal: half-length rows do not hold the TV / W half");
 #ifndef LPC_DOUBLE
   if constexpr (GdV2<RowP>::ok) {
+    if (a_done) {     // the rows of `a` were left in SB by m_admm_rows_hv: r_sp alone
+      constexpr int NB = GdV2<RowP>::NB;
+      return launch_k(e, LPC_K_ROW_FWD, k_rfwd_half_x_v2<NB, V2SK, RowPA, true>, dim3(e->g.Hp, e->P), NB, kV2Smem, e->g, *sc,
+                      row_arg(e), (const real2*)e->planW.tw, (const real*)e->admm.Rsp, (const real*)nullptr, (real*)nullptr,
+                      (const real*)nullptr, e->S, spec_b(e), make_fastdiv((unsigned)e->g.DC), make_fastdiv((unsigned)e->g.C));
+    }
     // the steady state of a call: xi half-applied on both sides, H V_old not read (xhalf_load); the first and the last
     // iteration of a call keep the first form -- the two agree bit for bit
     if ((e->plan.admm_rows_v2 & 1) && !sc->first && sc->xi_in && sc->xi_out && !(sc->xiw && sc->xi_store)) {
@@ -158,7 +176,8 @@ static int m_admm_rows_inv(Engine* e, real* Vout, real* HVout, int skip_hv_outsi
 // quads per lane and row with which the TV / W half can ride along: 1 or 2 (padded widths up to 8 x the lanes), else 0
 constexpr int kK1Quads = (RowP::n >> 2) <= RNT ? 1 : ((RowP::n >> 2) <= 2 * RNT ? 2 : 0);
 constexpr bool kK1Rows = kK1Quads != 0;
-static int m_admm_rows_fwd_x(Engine* e, const AdmmScalars* sc, const K1Rows* k1) {
+static int m_admm_rows_fwd_x(Engine* e, const AdmmScalars* sc, const K1Rows* k1, int a_done) {
+  if (a_done) return fail("internal: paired rows always transform `a`");
   real2 *SA = e->S, *SB = spec_b(e);
   // sc->skipa: `a` on the rows of the sensor window alone
   const int xrows = paired_rows_grid(e->g, sc->skipa != 0);
@@ -230,6 +249,12 @@ extern "C" int lpc_module_init(LpcModule* m, size_t engine_size, const char* src
   m->admm_rows_inv = m_admm_rows_inv;
 #if LPC_MOD_ROW_KIND == LPC_ROWS_HALF && !defined(LPC_DOUBLE)
   m->admm_rows_v2 = GdV2<RowP>::ok ? 1 : 0;
+#if LPC_MOD_ROW_X
+  // radix-16 row plans only: there the fused kernel compiles to the instructions of its two halves and agrees with them bit
+  // for bit on the GPU.  On 8.8.8 the compiler splits one packed FMA of the joined kernel into a multiply and an add (the
+  // trap described at xhalf_apply2) and the image moves by 1e-6 relative: not offered (profiles/hv_onchip_notes.md)
+  if (GdV2<RowP>::ok && GdV2<RowP>::R == 16) m->admm_rows_hv = m_admm_rows_hv;
+#endif
 #endif
 #if LPC_MOD_ROW_X
   m->admm_rows_fwd_x = m_admm_rows_fwd_x;

@@ -145,6 +145,8 @@ struct EngineOpts {
   int xi_half = 1;            // ... xi half-applied as well: the X half of the forward rows does not read H V_old inside the window
   int admm_rows_v2 = 1;       // half-length rows on a one-radix plan, second form (lpc_admm_v2_kernels.h): bit 0 the forward rows
                               // with the X half, bit 1 the inverse rows (measured slower at 12 MP: off by default); 0: first form
+  int hv_fuse = 1;            // ... and H V stays on chip between the steady-state iterations of a call (k_hv_rows_v2; needs bit 0 of
+                              // admm_rows_v2, hv_skip and xi_half).  1: the fused rows in front of the rows of V, 2: behind; 0: off
   // -- block orders (permutations: results unchanged)
   int rev_order = 9;          // bit 0 / 1 / 2 / 3: the tiled ADMM kernel / forward pass A / inverse pass A / the LDS middle walk
                               // their grids BACKWARDS: a kernel that starts where its predecessor finished finds the last
@@ -210,6 +212,7 @@ static inline std::string parse_engine_opts(const char* str, EngineOpts& o) {
       else if (k == "rho_rsp") o.rho_rsp = (int)iv;
       else if (k == "xi_half") o.xi_half = (int)iv;
       else if (k == "admm_rows_v2") o.admm_rows_v2 = (int)iv;
+      else if (k == "hv_fuse") o.hv_fuse = (int)iv;
       else if (k == "mid_pc") o.mid_pc = (int)iv;
       else if (k == "rev_order") o.rev_order = (int)iv;
       else if (k == "gd_rev") o.gd_rev = (int)iv;

@@ -351,6 +351,10 @@ void finish_plan(const lpc_config& c, const EngineOpts& o, const PlaneGeom& g, i
   // ... and rows wholly outside it skip the H V row transforms in both directions: the kept rows of SB are rescaled by
   // forward pass A (any plan) or, for single-pass columns, by the module's fused middle (option hv_full: off)
   pl.hv_skip = pl.xi_window && !o.hv_full && mod->admm_rows_inv && (split || mod->admm_mid);
+  // ... and in the steady state of a call the window's rows of H V stay in registers between the inverse row and the next
+  // iteration's forward row (k_hv_rows_v2: the forward rows' second form, float32; option hv_fuse=0: off, 2: behind the rows of V)
+  pl.hv_fuse = ((pl.admm_rows_v2 & 1) && pl.hv_skip && pl.xi_half && mod->admm_rows_hv && pl.k1 == ADMM_K1_TV_W) ? (o.hv_fuse & 3) : 0;
+  if (pl.hv_fuse == 3) pl.hv_fuse = 1;
   // ADMM middle.  Two arrays per lane: only short pass-B transforms fit the register file.  Measured at 12 MP
   // (profiles/r01b_notes.md): 24 points 0.89 ms and 32 points 0.83 ms beat the LDS middle (0.99 / 0.92 ms) but
   // need a 256- / 192-point pass A that costs more than it saves; 48 points is 1.62 ms (AGPR traffic).

@@ -281,7 +281,11 @@ __global__ __launch_bounds__(NT) void k_rinv_half(PlaneGeom g, PL plan, const re
   const long pl = LPC_BY(g);
   // AdmmScalars::skiphv: grid.x = 2 H + (Hp - H) -- both arrays on the rows of the sensor window, then A (= V) alone on
   // the rows above and below it (no empty workgroups: each would still claim its LDS and a launch slot)
-  if (skip_b_outside) {
+  // skip_b_outside == 2 (LaunchPlan::hv_fuse): grid.x = Hp, A alone -- the rows of B stay in the spectrum (k_hv_rows_v2)
+  if (skip_b_outside == 2) {
+    row = (int)bx;
+    arr = 0;
+  } else if (skip_b_outside) {
     if ((int)bx < 2 * g.H) row += g.sh;
     else {
       const int q = (int)bx - 2 * g.H;

@@ -50,14 +50,14 @@ int admm_rows_fwd(Engine* e) {
 }
 
 // ---- ADMM: the two work spectra -> V and H V (padded, no shift) ------------------------------------------------
-int admm_rows_inv(Engine* e, real* Vout, real* HVout, bool skip_hv_outside) {
-  if (e->mod && e->mod->admm_rows_inv) return e->mod->admm_rows_inv(e, Vout, HVout, skip_hv_outside ? 1 : 0);
-  if (skip_hv_outside) return fail("internal: skipping H V rows needs the plan module's row kernels");
+int admm_rows_inv(Engine* e, real* Vout, real* HVout, int hv_rows) {
+  if (e->mod && e->mod->admm_rows_inv) return e->mod->admm_rows_inv(e, Vout, HVout, hv_rows);
+  if (hv_rows != ADMM_HV_ROWS_ALL) return fail("internal: skipping H V rows needs the plan module's row kernels");
   const PlaneGeom& g = e->g;
   const Fft1dPlan& pinv = e->rows_r2 ? e->planWi : e->planW;
   if (e->plan.rows_half)
     return dispatch_row(g.Wp / 2, e->planWh.skew_ok, false, [&](auto NT, auto EM, auto SK, auto) {
-      return launch_admm_rows_inv_half<NT.value, EM.value, SK.value>(e, e->planWh, Vout, HVout, false);
+      return launch_admm_rows_inv_half<NT.value, EM.value, SK.value>(e, e->planWh, Vout, HVout, ADMM_HV_ROWS_ALL);
     });
   return dispatch_row(g.Wp, pinv.skew_ok, e->rows_r2, [&](auto NT, auto EM, auto SK, auto R2) {
     return launch_admm_rows_inv_paired<NT.value, EM.value, SK.value, R2.value, 0>(e, pinv, Vout, HVout, false);

@@ -60,6 +60,7 @@ struct lpc_rsrc { char* base; unsigned bytes; };
 static inline lpc_rsrc lpc_make_rsrc(const void* base, unsigned bytes) { lpc_rsrc r; r.base = (char*)base; r.bytes = bytes; return r; }
 static inline int lpc_opaque(int x) { return x; }
 static inline float lpc_opaque_f(float x) { return x; }
+template <class T2> static inline T2 lpc_opaque_v2(T2 x) { return x; }
 #define LPC_SCHED_FENCE() ((void)0)
 
 typedef void* lpcStream_t;
@@ -156,6 +157,14 @@ static __device__ __forceinline__ lpc_rsrc lpc_make_rsrc(const void* base, unsig
 static __device__ __forceinline__ int lpc_opaque(int x) { asm volatile("" : "+v"(x)); return x; }
 // (a float the optimiser knows nothing about: keeps a constant operand from merging two statements into one)
 static __device__ __forceinline__ float lpc_opaque_f(float x) { asm volatile("" : "+s"(x)); return x; }    // wave-uniform: stays scalar
+// (... per lane, a pair in two adjacent registers: a value computed in registers that must look to the optimiser like one
+// 8-byte load -- opaque, and one two-element vector as the seed for packed arithmetic; k_hv_rows_v2)
+static __device__ __forceinline__ float2 lpc_opaque_v2(float2 x) {
+  typedef float lpc_f2v __attribute__((ext_vector_type(2)));
+  lpc_f2v t = {x.x, x.y};
+  asm("" : "+v"(t));
+  return make_float2(t.x, t.y);
+}
 // nothing is scheduled across this point (keeps a batch of loads behind the arithmetic whose registers it needs)
 #define LPC_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 typedef hipStream_t lpcStream_t;
