@@ -174,10 +174,25 @@ int lpc_set_psf(lpc_handle h, const lpc_real* dev_psf, void* stream);
  * lpc_convolve_spectrum (n == cfg.batch: plane q of the input meets PSF plane q) and lpc_reconstruction_error work as
  * before.  Refused, with a message that says "per-frame":
  *     lpc_fista_record / lpc_admm_record with a non-zero argument, the four backward entries, and this call on a handle
- *     that records: gradients with per-frame PSFs are not implemented;
+ *     that records: gradients with per-frame PSFs are not implemented (unless lpc_per_frame_grad, below, switched them on);
  *     a gradient-descent handle without a pinned start value (lpc_set_start_value) and a schedule
  *     (lpc_set_fista_schedule): plain GD / Nesterov / FISTA take their step and start value from ONE PSF. */
 int lpc_set_psf_batch(lpc_handle h, const lpc_real* dev_psfs, void* stream);
+/* Gradients with one PSF per frame: a switch of the handle, off by default -- then every refusal above answers as written.
+ * lpc_per_frame_grad(h, 1): lpc_fista_record / lpc_admm_record work on a handle that holds per-frame PSFs,
+ * lpc_set_psf_batch works on a handle that records (it invalidates what was recorded, like lpc_set_psf, and the reset it
+ * implies starts the tape over), and the four backward entries run: frame b's state planes meet PSF b's spectrum in the
+ * replay, in every spectral step of the reverse sweeps and in the PSF-gradient terms, as in the forward.  The parameter
+ * gradients are summed over the frames as before; dev_grad_psf of the two _psf entries is then (B,D,H,W,C), PSF b's own
+ * gradient in slice b, nothing summed over the batch (on a handle with one PSF it stays (D,H,W,C)).  Every other refusal
+ * of the backward entries (odd padded lengths, depth > 1, the norm, ...) is unchanged.  Workspace of the PSF gradient on a
+ * per-frame handle:
+ *   ADMM   (4 * P + P) * Hp * cpitch * 2 * sizeof(lpc_real) bytes: the accumulator grows from C to P = B * C spectrum planes
+ *          (a handle whose workspace was allocated by a one-PSF backward gives it back and allocates this; it does not
+ *          shrink again before lpc_admm_record(h, 0));
+ *   FISTA  unchanged (lpc_fista_backward_psf): its accumulator is P planes already.
+ * lpc_per_frame_grad(h, 0) returns to the refusals; it frees nothing. */
+int lpc_per_frame_grad(lpc_handle h, int on);
 
 /* out = ifftshift(irfft2(rfft2(pad?(x)) * H or conj(H))) cropped if cfg.pad.
  * x: (n, D, Hx, Wx, x_channels), out: (n, D, Hx, Wx, C) with (Hx,Wx) = (H,W) if cfg.pad else (Hp,Wp);
@@ -254,10 +269,11 @@ int lpc_fista_backward(lpc_handle h, const lpc_real* dev_grad_out,   /* (B,D,H,W
  * call, counted in lpc_workspace_bytes, kept across a pause and freed with the tape by lpc_fista_record(h, 0):
  *   3 * P * Hp * cpitch * 2 * sizeof(lpc_real)  +  P * H * W * sizeof(lpc_real)      bytes,
  * P = B * C planes, cpitch = Wp / 2 + 1 rounded up to a multiple of 16 (Hp, Wp: lpc_padded_shape).  lpc_fista_backward
- * itself allocates and launches nothing of this.  dev_grad_psf NULL: lpc_fista_backward. */
+ * itself allocates and launches nothing of this.  dev_grad_psf NULL: lpc_fista_backward.  On a handle that holds one PSF
+ * per frame (lpc_set_psf_batch with lpc_per_frame_grad) nothing is summed over the batch: dev_grad_psf is (B,D,H,W,C). */
 int lpc_fista_backward_psf(lpc_handle h, const lpc_real* dev_grad_out, lpc_real* dev_grad_data, lpc_real* dev_grad_alpha,
                            lpc_real* dev_grad_coef, lpc_real* dev_grad_init,
-                           lpc_real* dev_grad_psf,    /* (D,H,W,C): w.r.t. the PSF                               */
+                           lpc_real* dev_grad_psf,    /* (D,H,W,C): w.r.t. the PSF; per-frame PSFs: (B,D,H,W,C)  */
                            void* stream);
 
 /* Reverse mode of the unrolled ADMM iterations (unrolled_admm.py:181-234 differentiated; what torch.autograd does in the
@@ -304,10 +320,13 @@ int lpc_admm_backward(lpc_handle h, const lpc_real* dev_grad_out,   /* (B,D,H,W,
  *   (4 * P + C) * Hp * cpitch * 2 * sizeof(lpc_real)      bytes,
  * P = B * C planes, cpitch = Wp / 2 + 1 rounded up to a multiple of 16 (Hp, Wp: lpc_padded_shape): the work spectra
  * F V_{i+1}, F rb, F a_i, F ab and the accumulator.  lpc_admm_backward itself allocates and launches nothing of this.
- * dev_grad_psf NULL: lpc_admm_backward. */
+ * dev_grad_psf NULL: lpc_admm_backward.  On a handle that holds one PSF per frame (lpc_set_psf_batch with
+ * lpc_per_frame_grad) nothing is summed over the batch: the accumulator is P planes, one thread per spectral point and
+ * state plane adds its frame's term with that frame's Hs, dev_grad_psf is (B,D,H,W,C), and the workspace is
+ * (4 * P + P) * Hp * cpitch * 2 * sizeof(lpc_real) bytes. */
 int lpc_admm_backward_psf(lpc_handle h, const lpc_real* dev_grad_out, lpc_real* dev_grad_data, lpc_real* dev_grad_mu1,
                           lpc_real* dev_grad_mu2, lpc_real* dev_grad_mu3, lpc_real* dev_grad_tau,
-                          lpc_real* dev_grad_psf,    /* (D,H,W,C): w.r.t. the PSF                                */
+                          lpc_real* dev_grad_psf,    /* (D,H,W,C): w.r.t. the PSF; per-frame PSFs: (B,D,H,W,C)   */
                           void* stream);
 
 /* ---- the hot loop: `for i in range(n_iter): self._update(i)`  recon.py:575-576 ------ */

@@ -112,6 +112,7 @@ class Lib:
             "lpc_padded_shape": [vp, ip, ip, ip, ip],
             "lpc_set_psf": [vp, fp, vp],
             "lpc_set_psf_batch": [vp, fp, vp],
+            "lpc_per_frame_grad": [vp, C.c_int],
             "lpc_convolve": [vp, fp, fp, C.c_int, C.c_int, C.c_int, vp],
             "lpc_convolve_spectrum": [vp, fp, fp, C.c_int, C.c_int, C.c_int, vp],
             "lpc_set_data": [vp, fp, C.c_int, vp],
@@ -246,6 +247,11 @@ class Handle:
     def set_psf_batch(self, ptr, stream=0):
         """one PSF per frame: ``ptr`` holds (batch, D, H, W, C) values (lpc_set_psf_batch); ``set_psf`` returns to one"""
         self._c(self.lib.dll.lpc_set_psf_batch(self.h, ptr, stream))
+
+    def per_frame_grad(self, on=True):
+        """gradients with one PSF per frame (lpc_per_frame_grad): the handle records with per-frame PSFs, takes them while
+        it records, and its backward entries run; ``grad_psf_ptr`` then holds (batch, D, H, W, C) values"""
+        self._c(self.lib.dll.lpc_per_frame_grad(self.h, int(bool(on))))
 
     def convolve(self, x_ptr, out_ptr, n, x_channels, adjoint, stream=0):
         self._c(self.lib.dll.lpc_convolve(self.h, x_ptr, out_ptr, n, int(x_channels), int(adjoint), stream))

@@ -26,9 +26,27 @@ class _Taped:
     (``"admm_record"`` / ``"fista_record"``), ``_solver`` the class in the messages."""
     _record_method = _solver = None
 
+    per_frame_grad = False                  # opt in (constructor): a forward that records takes per-frame PSFs
+
     def _tape_init(self):
         self._tape_gen = 0                  # counts the forwards: a backward of an earlier one finds its tape gone
         self._rec_state = (None, False)     # (the handle that holds the tape, is it recording)
+        if self.per_frame_grad:             # (the constructor's handle; _after_new_handle: every later one)
+            self._handle.per_frame_grad(1)
+
+    def _after_new_handle(self):
+        super()._after_new_handle()
+        if self.per_frame_grad:
+            self._handle.per_frame_grad(1)
+
+    def _active_psfs(self, psfs):
+        """the per-frame PSFs a recording forward with ``psfs=psfs`` differentiates (``per_frame_grad``): those handed in,
+        or those current since an earlier forward; None: one PSF for the batch"""
+        if not self.per_frame_grad:
+            return None
+        if psfs is None:
+            return self._psfs
+        return psfs if self._per_frame(psfs) else None
 
     def _record(self, on):
         """the handle keeps its tape from the next reset on, or stops: a forward without gradients between two
@@ -67,7 +85,9 @@ class _Taped:
 
     def _refuse_per_frame_training(self, psfs):
         """a forward that records, once ``train`` is known: per-frame PSFs -- handed in now, or current since an earlier
-        forward -- are inference only"""
+        forward -- are inference only, unless the solver was built with ``per_frame_grad=True``"""
+        if self.per_frame_grad:
+            return
         if self._per_frame(psfs) or self._psfs is not None:
             raise NotImplementedError(f"{self._solver}: gradients with per-frame PSFs (a 5-D psfs) are not implemented: "
                                       "run such a batch under torch.no_grad(), or give one PSF for the batch")

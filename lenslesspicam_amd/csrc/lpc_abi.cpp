@@ -113,8 +113,9 @@ int lpc_set_psf(lpc_handle e, const real* dev_psf, void* stream) {
 }
 
 // One PSF per frame (include/lpc.h).  What such a handle does not do names the reason with the word "per-frame"
+// -- unless lpc_per_frame_grad switched their gradients on
 static int per_frame_refusal(const Engine* e, const char* who) {
-  if (!e->psf_per_frame) return 0;
+  if (!e->psf_per_frame || e->per_frame_grad) return 0;
   return fail(std::string(who) + ": not available with per-frame PSFs (lpc_set_psf_batch): their gradients are not implemented");
 }
 // the gradient-descent family takes its step and its default start value from ONE PSF (gd.py:100-112): with one PSF per
@@ -128,7 +129,7 @@ static int per_frame_gd_check(const Engine* e, const char* who) {
 int lpc_set_psf_batch(lpc_handle e, const real* dev_psfs, void* stream) {
   if (!e || !dev_psfs) return fail("lpc_set_psf_batch: null argument");
   LPC_OK(per_frame_gd_check(e, "lpc_set_psf_batch"));
-  if (e->fista_tape.rec_on || e->admm_tape.rec_on)
+  if ((e->fista_tape.rec_on || e->admm_tape.rec_on) && !e->per_frame_grad)
     return fail("lpc_set_psf_batch: the handle records a tape, and gradients with per-frame PSFs are not implemented");
   e->stream = (lpcStream_t)stream;
   // |PsiT Psi| does not depend on the PSF: the finite-difference gram is made by the first PSF a handle gets, and a
@@ -140,6 +141,12 @@ int lpc_set_psf_batch(lpc_handle e, const real* dev_psfs, void* stream) {
   e->admm_tape.invalidate();
   if (gram) LPC_OK(admm_setup_constants(e));
   if (e->cfg.algo != LPC_ALGO_CONV) return lpc_reset(e, stream);
+  return 0;
+}
+
+int lpc_per_frame_grad(lpc_handle e, int on) {
+  if (!e) return fail("null handle");
+  e->per_frame_grad = on != 0;
   return 0;
 }
 

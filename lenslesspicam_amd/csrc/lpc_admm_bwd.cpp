@@ -66,7 +66,9 @@ static int psf_spectrum(Engine* e, const real* x, real2* S) {
 // (which k_admm_bwd_step of the same i overwrites); behind it the spectrum of rb and ONE k_admm_bwd_psf_acc.  After the
 // sweep the accumulator goes through the convolution middle as the multiplier of a unit impulse's spectrum (= 1
 // everywhere: the inverse column passes of the accumulator, 1 / (Hp Wp) folded in) and the inverse rows with the crop to
-// the PSF window.  Without grad_psf nothing changes.
+// the PSF window.  Without grad_psf nothing changes.  On a handle with one PSF per frame (lpc_per_frame_grad) the
+// accumulate is k_admm_bwd_psf_acc_frames, the accumulator, the unit spectra, the middle's multiplier and the inverse rows
+// are P planes instead of C, and grad_psf is (B,D,H,W,C).
 int admm_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_mu1, real* grad_mu2, real* grad_mu3,
                   real* grad_tau, real* grad_psf) {
   const PlaneGeom& g = e->g;
@@ -76,8 +78,12 @@ int admm_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_m
   const dim3 pw = grid1d((long)g.Hp * g.Wp, 256, e->P);
   const size_t sp = (size_t)g.cplane * e->P;
   real2 *FV = nullptr, *FR = nullptr, *FA = nullptr, *FB = nullptr, *acc = nullptr;
+  // one PSF per frame (lpc_set_psf_batch): nothing is summed over the batch, the accumulator holds a plane per state
+  // plane and grad_psf is (B,D,H,W,C).  Everything else of the sweep finds a frame's own spectrum through PlaneGeom::PM
+  // already: the replay's convolve_planar and admm_spectral_plain are the forward's
+  const int accP = e->psf_per_frame ? e->P : g.C;
   if (grad_psf) {
-    if (!t.psf_ws) LPC_OK(dev_alloc(e, &t.psf_ws, 2 * (4 * sp + (size_t)g.cplane * g.C)));      // (in reals: spectra)
+    LPC_OK(tape_psf_ws(e, t, 2 * (4 * sp + (size_t)g.cplane * accP)));      // (in reals: spectra)
     FV = (real2*)t.psf_ws; FR = FV + sp; FA = FR + sp; FB = FA + sp; acc = FB + sp;
   }
 
@@ -117,6 +123,12 @@ int admm_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_m
     LPC_OK(admm_spectral_plain(e, par, rbar, hr));
     if (grad_psf) {
       LPC_OK(psf_spectrum(e, rbar, FR));
+      if (e->psf_per_frame)
+        LPC_OK(launch_k(e, -1, k_admm_bwd_psf_acc_frames<256>, dim3((unsigned)((g.Wc + 255) / 256), (unsigned)g.Hp, (unsigned)e->P),
+                        256, 0, g, (real)(2.0 * par[0]), (const real2*)FV, (const real2*)FR, (const real2*)FA,
+                        (const real2*)FB, (const real2*)e->Hs, (const real2*)e->phr, (const real2*)e->phc, acc,
+                        i == n - 1 ? 1 : 0));
+      else
       LPC_OK(launch_k(e, -1, k_admm_bwd_psf_acc<256>, dim3((unsigned)((g.Wc + 255) / 256), (unsigned)g.Hp, (unsigned)g.C),
                       256, 0, g, e->cfg.batch, (real)(2.0 * par[0]), (const real2*)FV, (const real2*)FR, (const real2*)FA,
                       (const real2*)FB, (const real2*)e->Hs, (const real2*)e->phr, (const real2*)e->phc, acc,
@@ -144,10 +156,10 @@ int admm_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_m
     LPC_OK(fill_planar(e, rbar, 1, (real)1.));
     RealSrc unit = src_padded(e, rbar);
     unit.plane_stride = 0;
-    LPC_OK(rows_fwd_single(e, unit, FV, g.C, -1));
-    LPC_OK(conv_middle(e, FV, g.C, false, 0, g.Hp, true, acc, g.C));
-    LPC_OK(rows_inv_single(e, FV, dst_cropped(e, hr), g.C, -1));
-    LPC_OK(planar_to_hwc(e, hr, grad_psf, 1, g.H, g.W, g.W, g.uplane, 0, 0, 0));
+    LPC_OK(rows_fwd_single(e, unit, FV, accP, -1));
+    LPC_OK(conv_middle(e, FV, accP, false, 0, g.Hp, true, acc, accP));
+    LPC_OK(rows_inv_single(e, FV, dst_cropped(e, hr), accP, -1));
+    LPC_OK(planar_to_hwc(e, hr, grad_psf, accP / g.C, g.H, g.W, g.W, g.uplane, 0, 0, 0));
   }
   return 0;
 }

@@ -337,6 +337,30 @@ __global__ __launch_bounds__(NT) void k_admm_bwd_psf_acc(PlaneGeom g, int nframe
   acc[(long)c * g.cplane + off] = s;
 }
 
+// One PSF per frame (lpc_set_psf_batch; PlaneGeom::PM == all the planes): nothing is shared between the frames, so nothing
+// is summed.  One thread per spectral point (row blockIdx.y, column k) and STATE plane q (blockIdx.z): it reads Hs[q] and
+// the four work spectra at q and does one read-modify-write of acc[q] (`first`: a write) -- the term of
+// k_admm_bwd_psf_acc for one frame, in its order.  Seven streams of consecutive real2 along k per wave, no loop, no atomics.
+template <int NT>
+__global__ __launch_bounds__(NT) void k_admm_bwd_psf_acc_frames(PlaneGeom g, real two_m1, const real2* LPC_RESTRICT FV,
+                                                                 const real2* LPC_RESTRICT FR, const real2* LPC_RESTRICT FA,
+                                                                 const real2* LPC_RESTRICT FB, const real2* LPC_RESTRICT Hs,
+                                                                 const real2* LPC_RESTRICT phr, const real2* LPC_RESTRICT phc,
+                                                                 real2* LPC_RESTRICT acc, int first) {
+  const int k = (int)blockIdx.x * NT + (int)threadIdx.x;
+  if (k >= g.Wc) return;
+  const int row = blockIdx.y;
+  const long o = (long)blockIdx.z * g.cplane + (long)row * g.cpitch + k;
+  const real2 h = Hs[o];
+  const real w = -two_m1 * (phr[row].x * phc[k].x);      // phi is real: +-1
+  real2 s = first ? make_real2((real)0., (real)0.) : acc[o];
+  const real2 v = FV[o], r = FR[o], a = FA[o], ab = FB[o];
+  const real t = w * (r.x * v.x + r.y * v.y);             // -2 m1 phi Re(conj(F rb) F V_{i+1})
+  s.x += (v.x * ab.x + v.y * ab.y) + (r.x * a.x + r.y * a.y) + t * h.x;
+  s.y += (v.x * ab.y - v.y * ab.x) + (r.x * a.y - r.y * a.x) + t * h.y;
+  acc[o] = s;
+}
+
 // ---- the finishing sum of iteration i: block q adds quantity q of every workgroup in a fixed order ----------------------
 // g_mu1 = s0;  g_mu2 = s1 - s3 thr / m2;  g_mu3 = s2;  g_tau = s3 / m2        (thr = tau / m2)
 template <int NT>

@@ -224,7 +224,8 @@ struct FistaSchedule {
 // psf_ws, the PSF gradient's workspace, is ONE allocation too, made at its first call and freed with the tape:
 //   FISTA: three spectrum buffers of P planes (residual rows / cross term; full spectrum of P gz_i / rows of P Hg_i; full
 //       spectrum of P y_i) | the accumulator, P un-padded planes
-//   ADMM: four work spectra of P planes (F V_{i+1}, F rb, F a_i, F ab) | the accumulator, C spectrum planes
+//   ADMM: four work spectra of P planes (F V_{i+1}, F rb, F a_i, F ab) | the accumulator, C spectrum planes (one PSF per
+//       frame: P planes -- a backward that needs more room than psf_ws has gives it back and allocates it again)
 struct Tape {
   bool rec_on = false;
   real* buf = nullptr;
@@ -233,6 +234,7 @@ struct Tape {
   int n = 0;                   // iterations the tape was allocated for
   long iters = -1;             // iterations recorded since the last reset (-1: nothing recorded)
   real* psf_ws = nullptr;
+  size_t psf_ws_n = 0;         // elements psf_ws has room for
   real* at(long k) const { return buf + (size_t)k * slot; }
   void begin() { iters = 0; }
   void invalidate() { iters = -1; }      // what was recorded no longer matches the schedule / data / state: backward refuses
@@ -256,6 +258,7 @@ struct lpc_engine : LaunchCtx {
   int P = 0, Ppsf = 0, Pdata = 0;      // Ppsf: PSF planes in use = g.PM (DC, or P with one PSF per frame)
   int psf_cap = 0;                      // ... and the planes Hs, psf_planar, Hs_t, midc and midrd have room for
   bool psf_per_frame = false;           // lpc_set_psf_batch set the PSFs (until the next lpc_set_psf)
+  bool per_frame_grad = false;          // lpc_per_frame_grad: such a handle records and runs the backward entries
   std::vector<std::pair<void*, size_t>> allocs;   // every device allocation of the handle and its bytes (dev_alloc / dev_free)
   size_t total_bytes = 0;
 
@@ -309,7 +312,17 @@ static inline void tape_free(Engine* e, Tape& t) {
   dev_free(e, t.buf);
   dev_free(e, t.part);
   t.psf_ws = nullptr; t.buf = nullptr; t.part = nullptr; t.n = 0;
+  t.psf_ws_n = 0;
   t.invalidate();
+}
+// the PSF gradient's workspace of `count` elements: made at the first call, made again when a later call needs more
+static inline int tape_psf_ws(Engine* e, Tape& t, size_t count) {
+  if (t.psf_ws && t.psf_ws_n >= count) return 0;
+  dev_free(e, t.psf_ws);
+  t.psf_ws = nullptr; t.psf_ws_n = 0;
+  LPC_OK(dev_alloc(e, &t.psf_ws, count));
+  t.psf_ws_n = count;
+  return 0;
 }
 // for n iterations: nslots state arrays of `slot` elements and nparts partial sums, all or nothing (allocated for n: no-op)
 static inline int tape_alloc(Engine* e, Tape& t, int n, size_t nslots, size_t slot, size_t nparts) {

@@ -88,6 +88,8 @@ int gd_tape_push(Engine* e) {
 // passes (-> F(P y_i)), the forward's middle + residual rows (-> rows of P r_i), the column passes of a copy of the head's
 // rows (-> F(P gz_i)), the middle with F(P gz_i) as the multiplier + accumulate rows, and after MODE 1 the middle on a
 // copy of the rows of P Hg_i with F(P y_i) as the multiplier + accumulate rows.  Without grad_psf nothing changes.
+// One PSF per frame (lpc_per_frame_grad): the same launches -- every middle reads PSF plane q % PlaneGeom::PM = q -- and
+// the accumulator, one plane per state plane already, is laid out as (B,1,H,W,C) instead of summed over the batch.
 int gd_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_alpha, real* grad_coef,
                 real* grad_init, real* grad_psf) {
   const PlaneGeom& g = e->g;
@@ -111,7 +113,7 @@ int gd_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_alp
   real2 *W0 = nullptr, *W1 = nullptr, *W2 = nullptr;
   GdBwd pa{};          // the accumulate's arguments (MODE 3)
   if (grad_psf) {      // (Tape::psf_ws: three spectra, then the accumulator)
-    if (!t.psf_ws) LPC_OK(dev_alloc(e, &t.psf_ws, 6 * sp + (size_t)g.uplane * e->P));
+    LPC_OK(tape_psf_ws(e, t, 6 * sp + (size_t)g.uplane * e->P));
     W0 = (real2*)t.psf_ws; W1 = W0 + sp; W2 = W1 + sp;
     double s = 1.0;      // set_psf: the norm factor of the PSF spectrum
     if (e->cfg.norm == LPC_NORM_ORTHO) s = 1.0 / std::sqrt((double)g.Hp * (double)g.Wp);
@@ -157,7 +159,11 @@ int gd_backward(Engine* e, const real* grad_out, real* grad_data, real* grad_alp
   e->gd.fwd_done = false;     // S no longer holds the row spectra of the iterate
   LPC_OK(launch_k(e, -1, k_gd_bwd_finish<256>, dim3(C + 1, n), 256, gd_bwd_red_bytes<256>(), (const double*)t.part,
                   e->P, rows, C, (const real*)e->fista.galpha_sched, grad_alpha, grad_coef));
-  if (grad_psf) LPC_OK(gd_bwd_psf_sum(e, pa.gb, grad_psf));
+  // one PSF per frame (lpc_set_psf_batch): the accumulator's plane q is PSF q's own gradient -- no sum, only the layout,
+  // (B,1,H,W,C).  The sweep above needs nothing else: conv_middle finds a frame's spectrum through PlaneGeom::PM, the
+  // explicit multipliers are P planes already and the norm factor s is one number for every PSF
+  if (grad_psf && e->psf_per_frame) LPC_OK(planar_to_hwc(e, pa.gb, grad_psf, e->cfg.batch, g.H, g.W, g.W, g.uplane, 0, 0, 0));
+  else if (grad_psf) LPC_OK(gd_bwd_psf_sum(e, pa.gb, grad_psf));
   if (grad_init) LPC_OK(planar_to_hwc(e, a.gz, grad_init, e->cfg.batch, g.H, g.W, g.W, g.uplane, 0, 0, 0));
   if (grad_data) LPC_OK(gd_bwd_gdata(e, a.gb, grad_data));
   return 0;

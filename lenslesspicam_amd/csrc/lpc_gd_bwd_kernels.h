@@ -18,6 +18,7 @@
 //   MODE 3   rows (any spectrum buffer) -> irfft -> shift + crop = v -> acc (+)= -a_i s v, no transform afterwards:
 //            the PSF gradient's accumulate (lpc_fista_backward_psf).  Per iteration the sweep hands it two cross terms,
 //            v = K(conj(F(P gz_i)) . F(P r_i)) and v = K(conj(F(P y_i)) . F(P Hg_i)); k_gd_bwd_gpsf sums acc over the batch
+//            (one PSF per frame: no sum, k_planar_to_hwc lays acc out as (B,1,H,W,C))
 // The sums are deterministic: every workgroup (one image row, or one row pair) leaves its two partial sums, accumulated in
 // double, in a scratch array; k_gd_bwd_finish adds them up in a fixed order.  No atomics.
 #pragma once

@@ -270,7 +270,9 @@ int alloc_common(Engine* e) {
 
 // The handle holds n PSF planes from here on and addresses H by state plane q % n (PlaneGeom::PM): D*C planes, one PSF
 // for the batch, or batch*D*C, one per frame.  More planes than there is room for: Hs, psf_planar and ADMM's copies are
-// given back and allocated again for n planes (once per handle: they do not shrink)
+// given back and allocated again for n planes (once per handle: they do not shrink).  The reverse modes read the PSF
+// through the same launches as the forward (convolve_planar, conv_middle, admm_spectral_plain) and through
+// k_admm_bwd_psf_acc / k_admm_bwd_psf_acc_frames, chosen by psf_per_frame: nothing else holds a plane count of its own
 static int psf_planes(Engine* e, int n) {
   const PlaneGeom& g = e->g;
   if (n > e->psf_cap) {

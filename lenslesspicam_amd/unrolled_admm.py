@@ -24,14 +24,14 @@ conversion detaches -- the subclass travels with every tensor derived from it, t
 every other respect.  Not differentiated (``NotImplementedError``;
 from ``backward()`` for ``depth > 1``, frames whose padded height or width is odd and an initial estimate that asks for no
 gradient, so that their forward under autograd stays what it was -- it keeps no tape): the PSF unless the solver was
-built with ``psf_grad=True`` (``psfs=`` or a PSF requiring a gradient), per-frame PSFs (a 5-D ``psfs``), the initial
-estimate, a custom ``psi`` and a denoiser.
+built with ``psf_grad=True`` (``psfs=`` or a PSF requiring a gradient), per-frame PSFs (a 5-D ``psfs``) unless it was built with
+``per_frame_grad=True``, the initial estimate, a custom ``psi`` and a denoiser.
 
 Inference takes one PSF per measurement: ``forward(batch, psfs=P5)`` with ``P5.shape == (B,) + psf.shape`` under
 ``torch.no_grad()`` (or with nothing requiring a gradient) returns what B single-frame forwards with ``psfs=P5[b]`` return,
 in one launch sequence (``lpc_set_psf_batch``: the handle holds ``B D C`` PSF spectra).  ``P5`` stays current for later
 batches of B measurements, like the convolver the reference rebuilds and keeps (``trainable_recon.py:346-350``), until a
-4-D ``psfs=`` or ``_set_psf``; a forward that records refuses it.  ``background=`` and ``dist.*`` sharding of ``psfs`` are
+4-D ``psfs=`` or ``_set_psf``; a forward that records refuses it (unless ``per_frame_grad=True``, below).  ``background=`` and ``dist.*`` sharding of ``psfs`` are
 not supported.
 
 ``UnrolledADMM(psf, ..., psf_grad=True)`` makes the PSF an autograd input as well: ``forward(batch, psfs=p)`` with
@@ -43,6 +43,15 @@ transform at the end; the engine still works on its detached device copy of the 
 back by ``release_tape()``.  When nothing of the PSF requires a gradient the backward is ``lpc_admm_backward``, bit for
 bit.  ``norm`` must be ``"backward"`` (the default) for this gradient; one PSF for the batch.  The default is
 ``psf_grad=False``: every refusal above is unchanged.
+
+``UnrolledADMM(psf, ..., per_frame_grad=True)`` trains with one PSF per measurement: a forward that records takes a 5-D
+``psfs`` (handed in now, or current since an earlier forward) instead of refusing it, and ``backward()`` fills the
+parameters (summed over the frames, as autograd does), ``batch.grad`` and -- with ``psf_grad=True``, ``norm="backward"``
+and ``psfs.requires_grad`` -- ``psfs.grad`` of shape ``(B, D, H, W, C)``, PSF b's own gradient in slice b, nothing summed
+over the batch (``lpc_per_frame_grad``; the workspace's accumulator grows from C to ``P = B C`` spectrum planes).  Frame b
+of such a step has the bits of the single-frame step with ``psfs=P5[b]``.  Every other refusal stays; ``dist.*`` sharding
+of ``psfs`` and ``background=`` stay unsupported.  The default is ``per_frame_grad=False``: every message, workspace size
+and output bit is unchanged.
 
 Pre- / post-processor networks are not taken by the constructor: the measurement (and with ``psf_grad=True`` the PSF)
 gets a gradient, so compose them in torch around ``forward()`` -- ``post(rec(pre(batch), psfs=psf + net(psf)))`` trains
@@ -87,8 +96,9 @@ class _UnrolledADMMFunction(torch.autograd.Function):
         g_data = rec._empty((bshape[0],) + bshape[2:]) if need_b else None
         g_par = rec._empty((4, n))
         ptrs = (g.data_ptr(), None if g_data is None else g_data.data_ptr()) + tuple(g_par[k].data_ptr() for k in range(4))
-        if need_p:
-            g_psf = rec._empty(tuple(int(v) for v in rec._psf_shape))
+        if need_p:      # (a 5-D leaf: one PSF per measurement, one gradient each -- nothing summed over the batch)
+            frames = (bshape[0],) if len(ctx.psf_meta[0]) == 5 else ()
+            g_psf = rec._empty(frames + tuple(int(v) for v in rec._psf_shape))
             rec._handle.admm_backward_psf(*ptrs, g_psf.data_ptr(), rec._stream())
         else:      # (nothing of the PSF asks for a gradient: the parameter-only sweep, its bits and its cost)
             rec._handle.admm_backward(*ptrs, rec._stream())
@@ -111,7 +121,8 @@ class UnrolledADMM(_Taped, ADMM, torch.nn.Module):
     _record_method, _solver = "admm_record", "UnrolledADMM"
 
     def __init__(self, psf, dtype=None, n_iter=5, mu1=1e-6, mu2=1e-5, mu3=4e-5, tau=0.0001, psi=None,
-                 psi_adj=None, psi_gram=None, pad=False, norm="backward", skip_unrolled=False, psf_grad=False, **kwargs):
+                 psi_adj=None, psi_gram=None, pad=False, norm="backward", skip_unrolled=False, psf_grad=False,
+                 per_frame_grad=False, **kwargs):
         for key in ("pre_process", "post_process", "background_network", "psf_network", "compensation"):
             if kwargs.get(key) is not None:
                 raise NotImplementedError(f"{key}: learned components are outside the hot path (compose them in torch "
@@ -122,6 +133,7 @@ class UnrolledADMM(_Taped, ADMM, torch.nn.Module):
                          psi_gram=psi_gram, pad=pad, norm=norm, n_iter=n_iter, **kwargs)
         self.skip_unrolled = skip_unrolled
         self.psf_grad = bool(psf_grad)      # opt in: a PSF that requires a gradient is differentiated, not refused
+        self.per_frame_grad = bool(per_frame_grad)      # opt in: a forward that records takes a 5-D psfs
         # unrolled_admm.py:82-99: same attribute names as the reference so that checkpoints' state_dict entries can be
         # assigned; parameters unless skip_unrolled
         for name, val in zip(_NAMES, (mu1, mu2, mu3, tau)):
@@ -200,16 +212,19 @@ class UnrolledADMM(_Taped, ADMM, torch.nn.Module):
         params = [getattr(self, n) for n in _NAMES]
         psf_grad = (isinstance(psfs, torch.Tensor) and psfs.requires_grad) or \
             (isinstance(self._psf, torch.Tensor) and self._psf.requires_grad)
+        frames = self._active_psfs(psfs)      # per_frame_grad: the 5-D PSFs this forward runs with, and differentiates
+        psf_grad = psf_grad or (frames is not None and frames.requires_grad)
         init_grad = isinstance(self._initial_est, torch.Tensor) and self._initial_est.requires_grad
         train = torch.is_grad_enabled() and (psf_grad or init_grad or any(t.requires_grad for t in [batch] + params))
         if train:
             if self._per_frame(psfs):      # (a 4-D psfs below returns to one PSF: only the PSFs of THIS forward count)
                 self._refuse_per_frame_training(psfs)
-            self._refuse_gradients(batch, psfs if psf_grad else None)
+            self._refuse_gradients(batch, (frames if psfs is None else psfs) if psf_grad else None)
         self._take_psfs(batch, psfs)
         if train:
             self._refuse_per_frame_training(None)
-            psf = self._psf if self.psf_grad and isinstance(self._psf, torch.Tensor) and self._psf.requires_grad else None
+            psf = self._psf if frames is None else frames
+            psf = psf if self.psf_grad and isinstance(psf, torch.Tensor) and psf.requires_grad else None
             return _UnrolledADMMFunction.apply(self, batch, *params, psf).as_subclass(_Estimate)
         return self._run(batch)
 

@@ -22,13 +22,21 @@ its detached device copy).  As in the reference's ``forward(batch, psfs=...)``, 
 else (``trainable_recon.py:337-350``), the default start value and the steps derived from the constructor's PSF are
 constants.  The gradient costs a workspace of three spectra and one state array on top of the tape (include/lpc.h:
 ``lpc_fista_backward_psf``), allocated by the first backward that needs it and given back by ``release_tape()``.  One PSF
-for the batch: per-frame PSFs (a 5-D ``psfs``) raise ``NotImplementedError`` from a forward that records.
+for the batch: per-frame PSFs (a 5-D ``psfs``) raise ``NotImplementedError`` from a forward that records
+(unless the solver was built with ``per_frame_grad=True``, below).
 
 Inference takes one PSF per measurement: ``forward(batch, psfs=P5)`` with ``P5.shape == (B,) + psf.shape`` under
 ``torch.no_grad()`` (or with nothing requiring a gradient) returns what B single-frame forwards with ``psfs=P5[b]`` return,
 in one launch sequence (``lpc_set_psf_batch``).  ``P5`` stays current for later batches of B measurements until a 4-D
 ``psfs=`` or ``_set_psf``; the start value and ``_alpha_p`` stay the constructor's, as in the reference.  ``background=``
 and ``dist.*`` sharding of ``psfs`` are not supported.
+
+``UnrolledFISTA(psf, ..., per_frame_grad=True)`` trains with one PSF per measurement: a forward that records takes a 5-D
+``psfs`` (handed in now, or current since an earlier forward) instead of refusing it, and ``backward()`` fills the
+parameters (summed over the frames, as autograd does), ``batch.grad``, the initial estimate's gradient and, when
+``psfs.requires_grad``, ``psfs.grad`` of shape ``(B, D, H, W, C)`` with nothing summed over the batch
+(``lpc_per_frame_grad``; the same workspace).  Every other refusal stays.  The default is ``per_frame_grad=False``: every
+message, workspace size and output bit is unchanged.
 
 Pre- / post-processor networks are not taken by the constructor: the measurement and the PSF get gradients, so compose
 them in torch around ``forward()`` -- ``post(rec(pre(batch), psfs=psf + net(psf)))`` trains all of it.
@@ -71,7 +79,9 @@ class _UnrolledFISTAFunction(torch.autograd.Function):
         g_data = rec._empty((bshape[0],) + bshape[2:]) if need_b else None
         g_init = rec._empty(tuple(g.shape)) if need_i else None
         g_a, g_c = rec._empty((n, C)), rec._empty((n,))
-        g_psf = rec._empty(tuple(int(v) for v in rec._psf_shape)) if need_p else None
+        # (a 5-D leaf: one PSF per measurement, one gradient each -- nothing summed over the batch)
+        frames = (bshape[0],) if need_p and len(ctx.psf_meta[0]) == 5 else ()
+        g_psf = rec._empty(frames + tuple(int(v) for v in rec._psf_shape)) if need_p else None
         ptrs = (g.data_ptr(), None if g_data is None else g_data.data_ptr(), g_a.data_ptr(), g_c.data_ptr(),
                 None if g_init is None else g_init.data_ptr())
         if need_p:
@@ -101,12 +111,14 @@ class UnrolledFISTA(_Taped, FISTA, torch.nn.Module):
     def _before_psfs(self):
         self._push_schedule()       # (lpc_set_psf_batch refuses a gradient-descent handle without one)
 
-    def __init__(self, psf, n_iter=5, dtype=None, proj=non_neg, learn_tk=True, tk=1, skip_unrolled=False, **kwargs):
+    def __init__(self, psf, n_iter=5, dtype=None, proj=non_neg, learn_tk=True, tk=1, skip_unrolled=False,
+                 per_frame_grad=False, **kwargs):
         assert isinstance(psf, torch.Tensor), "UnrolledFISTA takes torch tensors, like the reference"
         torch.nn.Module.__init__(self)
         super().__init__(psf, dtype=dtype, proj=proj, tk=float(tk), n_iter=n_iter, **kwargs)
         C = int(self._psf_shape[3])
         self.skip_unrolled = skip_unrolled
+        self.per_frame_grad = bool(per_frame_grad)      # opt in: a forward that records takes a 5-D psfs
         # unrolled_fista.py:60-72: alpha initialised to 1.8 / max|H* H| per channel, for every iteration
         a0 = torch.as_tensor(np.asarray(self._alpha if not isinstance(self._alpha, torch.Tensor)
                                         else self._alpha.cpu().numpy(), dtype=np.float32))
@@ -187,12 +199,14 @@ class UnrolledFISTA(_Taped, FISTA, torch.nn.Module):
         self._check_forward_args(batch, psfs, background)
         init = self._initial_est if isinstance(self._initial_est, torch.Tensor) else None
         new_psf = psfs if isinstance(psfs, torch.Tensor) and psfs.dim() == 4 else self._psf
+        frames = self._active_psfs(psfs)      # per_frame_grad: the 5-D PSFs this forward runs with, and differentiates
         train = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
-                                                for t in (batch, self._alpha_p, self._tk_p, init, new_psf, psfs))
+                                                for t in (batch, self._alpha_p, self._tk_p, init, new_psf, psfs, frames))
         if train and self._per_frame(psfs):
             self._refuse_per_frame_training(psfs)
         self._take_psfs(batch, psfs)
-        psf = self._psf if isinstance(self._psf, torch.Tensor) and self._psf.requires_grad else None
+        psf = self._psf if frames is None else frames
+        psf = psf if isinstance(psf, torch.Tensor) and psf.requires_grad else None
         if train:
             self._refuse_per_frame_training(None)
             if self._hook:
